@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DyCON training-step benchmark on MI355X (contract: see the task description / DESIGN.md section 4).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -29,6 +29,37 @@ F32_MFMA_KERNELS = ("conv_wgrad_kernel", "conv_direct_kernel", "head_1x1", "grad
 ALGORITHMIC_PER_VOLUME = {("vnet", (96, 96, 96)): (1.186e9, 282.9e9), ("vnet", (112, 112, 80)): (1.345e9, 320.9e9),
                           ("vnet", (112, 112, 96)): (1.614e9, 385.0e9), ("unet_3D", (96, 96, 96)): (1.657e9, 491.8e9),
                           ("unet_3D", (112, 112, 80)): (1.879e9, 557.8e9)}
+DUMP_CAP = 1 << 21              # elements kept per dumped array (8 MB in float32; the default bench step dumps 46 MB in all)
+DUMP_BUDGET = 64 << 20          # bytes, all dumped arrays together
+
+
+def dump_outputs(out, tr, dirname):
+    """--dump-outputs: what the last timed step computed, as <dirname>/<name>.npy -- every entry of the dict DyconTrainer.step returned
+    (losses, logits, features, FeCL mask, schedule scalars) and the updated weights (`student_weights` / `teacher_weights`: the
+    floating-point entries of state_dict() / teacher_state_dict(), flattened and concatenated in their order).  Tensors are stored in
+    float32 (float64 ones in float64), Python numbers as float64 0-d arrays.  An array of more than DUMP_CAP elements is replaced by
+    DUMP_CAP of its row-major elements at positions drawn with a fixed seed, the same positions in every run of the same shapes."""
+    import numpy as np
+    arrays = dict(out)
+    arrays["student_weights"] = torch.cat([v.reshape(-1).float() for v in tr.state_dict().values() if v.is_floating_point()])
+    arrays["teacher_weights"] = torch.cat([v.reshape(-1).float() for v in tr.teacher_state_dict().values() if v.is_floating_point()])
+    host = {}
+    for name, v in arrays.items():
+        if not torch.is_tensor(v):
+            host[name] = np.asarray(float(v), dtype=np.float64)
+            continue
+        v = v.detach().cpu()
+        v = v.double() if v.dtype == torch.float64 else v.float()
+        if v.numel() > DUMP_CAP:
+            pos = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_CAP, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(pos)]
+        host[name] = v.numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget (lower DUMP_CAP)")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(model, patch, seed):
@@ -76,9 +107,10 @@ def cpu_baseline(model, patch, seed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)      # warm-up 10, time >= 50 steps (60 steps = 0.4 s on the GPU)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (SURVEY 8d: warm-up 10, time >= 50 steps)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=3, help="the timed region is run this many times; the median repeat is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="the timed region of --steps steps is run this many times; the median "
+                                                            "repeat is reported")
     ap.add_argument("--model", default="vnet", choices=["vnet", "unet_3D"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=4)
@@ -89,7 +121,11 @@ def main():
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--strict", action="store_true", help="exit non-zero when the per-kernel table fails its self-check")
     ap.add_argument("--cfg", default="", help="diagnostics: TrainConfig overrides, e.g. overlap_wgrad=False,overlap_teacher=False")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0; "
+                                                          "see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -138,11 +174,11 @@ def main():
     for _ in range(args.warmup):
         tr.step(vol, lab)
     barrier()
-    # SURVEY 8d protocol: the timed region is run REPEATS times back to back inside this invocation (each: exactly --steps steps
-    # between two barriers + synchronisations, max over ranks) and the MEDIAN repeat is reported; `ms_per_step_repeats` keeps all
+    # the timed region is exactly --steps steps between two barriers + synchronisations (max over ranks); with --repeats N it is run
+    # N times back to back inside this invocation and the MEDIAN repeat is reported; `ms_per_step_repeats` keeps all
     note("timed region")
     repeats = []
-    for _ in range(max(1, args.repeats)):
+    for _ in range(args.repeats):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -155,6 +191,8 @@ def main():
             dt = float(t)
         repeats.append(dt)
     dt = sorted(repeats)[len(repeats) // 2]
+    if args.dump_outputs and rank == 0:     # before the profiled steps below: the returned tensors are valid until the next step
+        dump_outputs(out, tr, args.dump_outputs)
     ms_per_step = dt / args.steps * 1e3
     value = args.batch * world * args.steps / dt
     note(f"{ms_per_step:.3f} ms/step (repeats: {', '.join(f'{r / args.steps * 1e3:.3f}' for r in repeats)}), {value:.2f} volumes/s")

@@ -171,26 +171,35 @@ def _stats(t):
 
 
 def test_full_nets():
+    """fp32 against the fp32 fixture, and the same inputs and weights in fp64 against the fixture's fp64 twin.  In fp32, the signed
+    sum of a gradient (block_five.conv.0.weight: -3e-10 in fp64 beside a sum of |g| of 1.4e7) and every statistic of a gradient that
+    is zero in exact arithmetic (the conv biases in front of a normalisation: sum of |g| 2e-11 in fp64, 1e-2 in fp32) are round-off
+    that follows the host's convolution summation order; the fp64 run pins them, with everything else."""
     g = load_golden("full_nets")
-    rng = np.random.default_rng(int(g["x_seed"]))
-    draw = lambda *s: T(rng.standard_normal(s).astype(np.float32))  # noqa: E731
-    x = draw(2, 1, 32, 32, 32)
-    for kind, mk in (("vnet", ON.make_vnet_params), ("unet", ON.make_unet_params)):
-        p = mk(int(g[f"{kind}.param_seed"]))
-        names = list(ON.trainable(p))
-        leaves = {k: p[k].clone().requires_grad_(True) for k in names}
-        sdf, logits, feats = ON.forward("vnet" if kind == "vnet" else "unet_3D", x, {**p, **leaves})
-        close(logits[..., ::2, ::2, ::2], g[f"{kind}.logits_sub"], 1e-4, 2e-5)
-        close(feats, g[f"{kind}.feats"], 1e-4, 2e-5)
-        r1, r2 = draw(*logits.shape), draw(*feats.shape)
-        obj = (logits * r1).sum() + (feats * r2).sum()
-        grads = torch.autograd.grad(obj, [leaves[k] for k in names], allow_unused=True)
-        assert list(g[f"{kind}.grad_names"]) == names
-        for k, gr, ref in zip(names, grads, g[f"{kind}.grad_stats"]):
-            if gr is None:
-                assert k.startswith("final.") and not ref.any()
-                continue
-            np.testing.assert_allclose(_stats(gr), ref, rtol=2e-3, atol=5e-3, err_msg=k)
+    for dtype, suffix in ((torch.float32, ""), (torch.float64, ".f64")):
+        rng = np.random.default_rng(int(g["x_seed"]))
+        draw = lambda *s: T(rng.standard_normal(s).astype(np.float32)).to(dtype)  # noqa: E731
+        x = draw(2, 1, 32, 32, 32)
+        for kind, mk in (("vnet", ON.make_vnet_params), ("unet", ON.make_unet_params)):
+            p = {k: v.to(dtype) if v.is_floating_point() else v for k, v in mk(int(g[f"{kind}.param_seed"])).items()}
+            names = list(ON.trainable(p))
+            leaves = {k: p[k].clone().requires_grad_(True) for k in names}
+            sdf, logits, feats = ON.forward("vnet" if kind == "vnet" else "unet_3D", x, {**p, **leaves})
+            tol = (1e-4, 2e-5) if dtype == torch.float32 else (1e-9, 1e-9)
+            close(logits[..., ::2, ::2, ::2], g[f"{kind}.logits_sub{suffix}"], *tol)
+            close(feats, g[f"{kind}.feats{suffix}"], *tol)
+            r1, r2 = draw(*logits.shape), draw(*feats.shape)
+            obj = (logits * r1).sum() + (feats * r2).sum()
+            grads = torch.autograd.grad(obj, [leaves[k] for k in names], allow_unused=True)
+            assert list(g[f"{kind}.grad_names"]) == names
+            for k, gr, ref, ref64 in zip(names, grads, g[f"{kind}.grad_stats{suffix}"], g[f"{kind}.grad_stats.f64"]):
+                if gr is None:
+                    assert k.startswith("final.") and not ref.any()
+                    continue
+                if dtype == torch.float64:
+                    np.testing.assert_allclose(_stats(gr), ref, rtol=1e-9, atol=1e-6, err_msg=k)
+                elif ref64[1] > 1e-6:           # sum of |g| and of g^2 of a non-zero gradient
+                    np.testing.assert_allclose(_stats(gr)[1:], ref[1:], rtol=2e-3, atol=5e-3, err_msg=k)
 
 
 @pytest.mark.parametrize("kind", ["unet", "vnet"])
