@@ -467,6 +467,161 @@ __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(con
         }
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// k=3 convolution of the small levels in ONE launch (bf16, Cin = 128, N % 128 == 0): the split-K of conv_k3_tile_kernel done
+// inside the workgroup, with the same arithmetic.
+//
+// One workgroup = a 4x4x4 voxel block of one sample (64 rows, ragged blocks masked) x 64 output columns, 8 waves.
+//  * The block's 6x6x6 x 128 halo is staged into LDS once (zero padding written at staging time): every one of the 27 taps is then
+//    an address offset into the image.  A voxel row is 256 B = one bank row; its sixteen 16-byte channel slots are XOR-swizzled by
+//    4 (y & 3) + (x & 3) of the halo voxel, so the 16 rows x 4 k-groups of an A fragment hit 16 distinct slots in every
+//    ds_read_b128 lane group.
+//  * The 108 k-steps are cut into the S contiguous ranges of conv_tile_plan (S <= 4), exactly as the split-K launch would cut them.
+//    Range z is ONE chain of MFMAs in k order, owned by 4 / NJ waves that each take NJ of the 4 column tiles: the same fp32
+//    accumulation as a split of conv_k3_tile_kernel.  B fragments go global -> registers, one k-step ahead, never through LDS.
+//  * The partials are summed in the LDS the halo used, 32 columns per round, in the finish's order: ((bias + p_0) + p_1) + ...,
+//    then `accumulate`, bf16 rounding and 16-byte row stores.  The result is bit for bit that of conv_k3_tile + splitk_finish.
+// No slab, no finish launch: 26.2 -> 13.8 us per 128 -> 128 convolution at 12^3, B = 4.
+// ------------------------------------------------------------------------------------------------
+constexpr int CH_T = 4, CH_H = CH_T + 2, CH_NH = CH_H * CH_H * CH_H;    // 4^3 output block, 6^3 halo
+constexpr int CH_CIN = 128;                                               // input channels (256-B voxel rows)
+constexpr int CH_KS = 27 * CH_CIN / 32;                                   // k-steps
+constexpr int CH_NW = 8;                                                  // waves per workgroup
+constexpr int CH_MAXS = 4;                                                // most split ranges (one per 2 waves)
+constexpr int CH_HALO_BYTES = CH_NH * CH_CIN * 2;                         // 55296
+constexpr int CH_RED_BYTES = CH_MAXS * 8 * 1024;                          // up to four 64 x 32 fp32 partials
+constexpr int CH_MAIN_BYTES = CH_HALO_BYTES > CH_RED_BYTES ? CH_HALO_BYTES : CH_RED_BYTES;
+constexpr int CH_OP = 64 + 8;                                             // bf16 row pitch of the output image (144 B)
+
+// NJ = column tiles per wave (2: S 3..4, 1: S 1..2).  4 waves per SIMD and 63 KB of LDS: two workgroups share a CU,
+// so the teacher's launches on the side stream can run beside the student's.
+template <int NJ>
+__global__ __launch_bounds__(64 * CH_NW) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void conv_k3_halo_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf, const float* __restrict__ bias, bf16* __restrict__ Y,
+                         int D, int H, int W, int N, int NT, int tz, int ty, int tx, int S, int kc_per_split, int accumulate) {
+    constexpr int WPS = 4 / NJ;                                           // waves per split range
+    __shared__ __attribute__((aligned(16))) unsigned char lds[CH_MAIN_BYTES + 64 * CH_OP * 2];
+    unsigned short* ot = reinterpret_cast<unsigned short*>(lds + CH_MAIN_BYTES);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = lane & 15, kg = lane >> 4, ry = r >> 2, rx = r & 3;
+    int q = blockIdx.x;
+    const int bx = q % tx; q /= tx;
+    const int by = q % ty; q /= ty;
+    const int bz = q % tz;
+    const int b = q / tz;
+    const int z0 = bz * CH_T, y0 = by * CH_T, x0 = bx * CH_T;
+    const int nt0 = blockIdx.y * 4;
+    const int zs = wave / WPS, cg = wave % WPS;                           // this wave: split range zs, column tiles cg * NJ ...
+    const int k0 = zs * kc_per_split, k1 = min(CH_KS, k0 + kc_per_split);
+    const bf16* xb = X + (long long)b * D * H * W * CH_CIN;
+
+    // stage the halo: 216 voxels x 16 slots of 16 B, zero outside the volume
+    {
+        constexpr int PIECES = CH_NH * 16, PER = (PIECES + 64 * CH_NW - 1) / (64 * CH_NW);
+        uint4 v[PER];
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int p = tid + i * 64 * CH_NW, hv = p >> 4, sl = p & 15;
+            const int hz = hv / 36, hy = (hv / 6) % 6, hx = hv % 6;
+            const int zi = z0 + hz - 1, yi = y0 + hy - 1, xi = x0 + hx - 1;
+            v[i] = make_uint4(0, 0, 0, 0);
+            if (p < PIECES && (unsigned)zi < (unsigned)D && (unsigned)yi < (unsigned)H && (unsigned)xi < (unsigned)W)
+                v[i] = *reinterpret_cast<const uint4*>(xb + (((long long)zi * H + yi) * W + xi) * CH_CIN + sl * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int p = tid + i * 64 * CH_NW, hv = p >> 4, sl = p & 15;
+            const int hy = (hv / 6) % 6, hx = hv % 6;
+            if (p < PIECES) *reinterpret_cast<uint4*>(lds + hv * 256 + ((sl ^ (4 * (hy & 3) + (hx & 3))) * 16)) = v[i];
+        }
+    }
+
+    // B fragments of k-step kc (tap kc / 4, 32-channel quarter kc % 4): the wave's NJ column tiles, 1 KB each
+    auto load_b = [&](int kc, uint4 (&bf)[NJ]) {
+        const uint4* p = reinterpret_cast<const uint4*>(Wf + ((long long)kc * NT + nt0 + cg * NJ) * 512) + lane;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) bf[j] = p[j * 64];
+    };
+    f32x4 acc[4][NJ];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[m][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    auto compute = [&](int kc, const uint4 (&bf)[NJ]) {
+        const int t = kc >> 2, kq = kc & 3;
+        const int dz = t / 9, dy = (t / 3) % 3, dx = t % 3;               // wave-uniform
+        const int hy = ry + dy, hx = rx + dx;
+        const int slot = (4 * kq + kg) ^ (4 * (hy & 3) + (hx & 3));
+        const unsigned char* ap = lds + ((dz * CH_H + hy) * CH_H + hx) * 256 + slot * 16;
+        bf16x8 a[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) a[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ap + m * CH_H * CH_H * 256));
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], __builtin_bit_cast(bf16x8, bf[j]), acc[m][j], 0, 0, 0);
+    };
+
+    __syncthreads();
+    if (k0 < k1) {                                                        // waves beyond the plan's S ranges have no k-steps
+        // the range's k-steps in order, two per iteration in register stages b0 / b1 (each refilled one k-step ahead of its use)
+        uint4 b0[NJ], b1[NJ];
+        int kc = k0;
+        load_b(kc, b0);
+        if (kc + 1 < k1) load_b(kc + 1, b1);
+        while (true) {
+            compute(kc, b0);
+            if (kc + 2 < k1) load_b(kc + 2, b0);
+            if (++kc >= k1) break;
+            compute(kc, b1);
+            if (kc + 2 < k1) load_b(kc + 2, b1);
+            if (++kc >= k1) break;
+        }
+    }
+    __syncthreads();                                                      // the halo is dead: its LDS takes the partials
+
+    // the finish, 32 columns (column tiles 2h, 2h + 1 of the block) per round: partial of range z at red + z * 2048
+    float* red = reinterpret_cast<float*>(lds);
+    const int T = tid >> 6, rm = T >> 1, rj = T & 1;                       // reducer: tile (m-tile rm, column tile rj of the round), lane `lane`
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (k0 < k1) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int jt = cg * NJ + j;
+                if ((jt >> 1) != h) continue;
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    *reinterpret_cast<f32x4*>(red + zs * 2048 + ((m * 2 + (jt & 1)) * 64 + lane) * 4) = acc[m][j];
+            }
+        }
+        __syncthreads();
+        const int col = (2 * h + rj) * 16 + r;                            // column inside the 64-wide block
+        const int n = nt0 * 16 + col;
+        const float bv = bias ? bias[n] : 0.f;
+        f32x4 o = f32x4{bv, bv, bv, bv};
+        for (int z = 0; z < S; ++z) o += *reinterpret_cast<const f32x4*>(red + z * 2048 + tid * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = rm * 16 + kg * 4 + i;                         // voxel (z0 + rm, y0 + kg, x0 + i)
+            float v = o[i];
+            if (accumulate) {
+                const int zo = z0 + rm, yo = y0 + kg, xo = x0 + i;
+                if (zo < D && yo < H && xo < W) v += ldf(Y + ((((long long)b * D + zo) * H + yo) * W + xo) * N + n);
+            }
+            ot[row * CH_OP + col] = f32_to_bf16_bits(v);
+        }
+        __syncthreads();
+    }
+    // 64 rows x 128 B: one 16-byte piece per thread
+    const int row = tid >> 3, pc = tid & 7;
+    const int zo = z0 + (row >> 4), yo = y0 + ((row >> 2) & 3), xo = x0 + (row & 3);
+    if (zo < D && yo < H && xo < W)
+        *reinterpret_cast<uint4*>(Y + ((((long long)b * D + zo) * H + yo) * W + xo) * N + nt0 * 16 + pc * 8) =
+            *reinterpret_cast<const uint4*>(ot + row * CH_OP + pc * 8);
+}
+
 // ------------------------------------------------------------------------------------------------
 // k=3 convolution with an LDS-staged halo tile (bf16): the large spatial levels.
 //
@@ -3138,6 +3293,14 @@ static SplitK conv_tile_plan(long long M, int N, int Cin) {
     p.splits = (nKC + p.kc_per_split - 1) / p.kc_per_split;
     return p;
 }
+// one-launch kernel for the small levels (conv_k3_halo_kernel: the split of conv_tile_plan done inside the workgroup, no slab, same
+// bits): taken ahead of conv_k3_tile for 128 input channels when the plan has at most 4 ranges (the 12^3 and 14x14x10 levels at
+// B = 4; a 64-column range per wave, for 5..8 ranges, spills at the register budget of two workgroups per CU).  At Cin = 256 (the
+// 6^3 level) a 64-column halo kernel measured even with conv_k3_tile<2> + finish (19.3 against 19.2 us): each
+// workgroup there streams 884 KB of weights and only 128 workgroups run; that level keeps its split-K slabs.
+static bool conv_halo_ok(int dtype, int mode, int scatter, long long M, long long DHW, int Cin, int N) {
+    return conv_tile_ok(dtype, mode, scatter, DHW, Cin, N) && Cin == CH_CIN && conv_tile_plan(M, N, Cin).splits <= CH_MAXS;
+}
 
 extern "C" int dycon_pack_batch(const dycon_pack_job_t* jobs_dev, int njobs, int blocks_per_job, dycon_stream_t stream) {
     DYCON_REQUIRE(jobs_dev && njobs > 0 && njobs <= 65535 && blocks_per_job > 0, "pack_batch: bad arguments");
@@ -3172,6 +3335,7 @@ extern "C" size_t dycon_conv_gemm_workspace(int dtype, int mode, int scatter, in
     int Do, Ho, Wo;
     row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
     const long long M = (long long)B * Do * Ho * Wo;
+    if (conv_halo_ok(dtype, mode, scatter, M, (long long)Di * Hi * Wi, Cin, N)) return 0;
     const SplitK sk = conv_tile_ok(dtype, mode, scatter, (long long)Di * Hi * Wi, Cin, N) ? conv_tile_plan(M, N, Cin)
                                                                                        : splitk_plan(dtype, mode, scatter, M, N, Cin);
     return sk.splits > 1 ? (size_t)sk.splits * M * N * sizeof(float) : 0;
@@ -3181,6 +3345,7 @@ extern "C" int dycon_conv_gemm_splits(int dtype, int mode, int scatter, int B, i
     int Do, Ho, Wo;
     row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
     const long long M = (long long)B * Do * Ho * Wo;
+    if (conv_halo_ok(dtype, mode, scatter, M, (long long)Di * Hi * Wi, Cin, N)) return 1;
     const SplitK sk = conv_tile_ok(dtype, mode, scatter, (long long)Di * Hi * Wi, Cin, N) ? conv_tile_plan(M, N, Cin)
                                                                                        : splitk_plan(dtype, mode, scatter, M, N, Cin);
     return sk.splits;
@@ -3308,6 +3473,17 @@ extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float*
             else DYCON_CL(32, 4, 2);
         }
 #undef DYCON_CL
+        DYCON_LAUNCH_CHECK();
+        return DYCON_OK;
+    }
+    if (conv_halo_ok(dtype, mode, scatter, (long long)B * Di * Hi * Wi, (long long)Di * Hi * Wi, Cin, N)) {
+        const long long M = (long long)B * Di * Hi * Wi;
+        const int tz = cdiv(Di, CH_T), ty = cdiv(Hi, CH_T), tx = cdiv(Wi, CH_T);
+        const SplitK sk = conv_tile_plan(M, N, Cin);
+        const dim3 grid(B * tz * ty * tx, N / 64);
+#define DYCON_CH(NJV) conv_k3_halo_kernel<NJV><<<grid, 64 * CH_NW, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, Di, Hi, Wi, N, N / 16, tz, ty, tx, sk.splits, sk.kc_per_split, accumulate)
+        if (sk.splits > 2) DYCON_CH(2); else DYCON_CH(1);
+#undef DYCON_CH
         DYCON_LAUNCH_CHECK();
         return DYCON_OK;
     }

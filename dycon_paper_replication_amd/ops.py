@@ -311,6 +311,9 @@ def conv_gemm(x, wfrag, bias, mode, N, Cout, scatter=False, out=None, accumulate
     lds_path = mode == CONV_K3 and not scatter and conv_uses_lds(x, Cin, Cout)
     if lds_path:      # the persistent kernels of the 16-channel level, or the generic LDS-halo kernel
         rname = "conv_k3_p16" if (Cin, Cout) == (16, 16) else ("conv_k3_c1" if Cin == 1 else "conv_k3_lds")
+    elif (mode == CONV_K3 and not scatter and x.dtype == torch.bfloat16 and Cin == 128 and N % 128 == 0 and D * H * W < 13824
+          and not nws):
+        rname = "conv_k3_halo"      # the small levels' one-launch kernel (split-K ranges inside the workgroup: no workspace)
     elif (mode == CONV_K3 and not scatter and x.dtype == torch.bfloat16 and Cin % 32 == 0 and Cin >= 64 and N % 128 == 0
           and D * H * W < 13824):
         rname = "conv_k3_tile"
