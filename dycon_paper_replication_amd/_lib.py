@@ -101,6 +101,8 @@ SIGNATURES = {
     "dycon_sw_finalize": (I, [P, P, L, F, P, P, P]),
     "dycon_binary_overlap": (I, [P, P, I, L, P, P]),
     "dycon_batch_overlap": (I, [P, P, I, I, L, P, P]),
+    "dycon_simhist_workspace": (Z, [I, I, I, I]),
+    "dycon_simhist": (I, [P, P, I, I, I, I, F, I, P, P, P, P, Z, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

@@ -764,6 +764,33 @@ def fecl_bwd(feat, teacher, mask, gambling, temperature, gamma, use_focal, cross
     return g
 
 
+def similarity_histograms(feat, mask, tau=0.6, bins=50):
+    """Histograms of the positive- and negative-pair similarities monitor.monitor_similarity_distributions draws
+    (utils/monitor.py:7-50), built blockwise on the GPU without the (B, N, N) matrix.  feat (B, N, Dm) fp32 / bf16 raw rows
+    (normalised here, as F.normalize), Dm <= 256; mask (B, N) or (B, 1, N) labels, a pair is positive when its two labels are
+    equal.  Returns device tensors (counts[2, bins] int64, edges[2, bins + 1] fp32, minmax[4] fp32): row 0 positive, row 1
+    negative, binned as np.histogram(values, bins) bins the float32 values; minmax = pos lo, hi, neg lo, hi.  No host sync."""
+    if not (torch.is_tensor(feat) and feat.is_cuda and torch.is_tensor(mask) and mask.is_cuda):
+        raise ValueError("similarity_histograms: feat and mask must be CUDA tensors (a HIP kernel builds the histograms; "
+                         "there is no CPU path)")
+    if feat.dim() != 3:
+        raise ValueError(f"similarity_histograms: feat must be (B, N, Dm), got {tuple(feat.shape)}")
+    B, N, Dm = feat.shape
+    if not 1 <= int(bins) <= 256:
+        raise ValueError(f"similarity_histograms: bins = {bins} outside 1..256")
+    if tuple(mask.shape) not in ((B, N), (B, 1, N)):
+        raise ValueError(f"similarity_histograms: mask must be ({B}, {N}) or ({B}, 1, {N}), got {tuple(mask.shape)}")
+    feat = feat.detach().contiguous()
+    mask = mask.detach().reshape(B, N).to(torch.float32).contiguous()
+    counts = torch.empty((2, bins), dtype=torch.int64, device=feat.device)
+    edges = torch.empty((2, bins + 1), dtype=torch.float32, device=feat.device)
+    minmax = torch.empty(4, dtype=torch.float32, device=feat.device)
+    ws = _ws(query("dycon_simhist_workspace", B, N, Dm, bins), feat)
+    call("dycon_simhist", _p(feat), _p(mask), dt(feat), B, N, Dm, float(tau), int(bins), _p(counts), _p(edges), _p(minmax),
+         _p(ws), ws.numel() * 4, _s())
+    return counts, edges, minmax
+
+
 # ------------------------------------------------------------------ optimiser
 def sumsq(g, out):
     call("dycon_sumsq", _p(g), g.numel(), _p(out), _s())

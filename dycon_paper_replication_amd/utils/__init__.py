@@ -1,1 +1,1 @@
-from . import dycon_losses, losses, ramps  # noqa: F401
+from . import dycon_losses, losses, monitor, ramps  # noqa: F401

@@ -419,6 +419,18 @@ int dycon_binary_overlap(const uint8_t* pred, const void* gt, int gt_bytes, long
 int dycon_batch_overlap(const float* logits, const void* gt, int gt_bytes, int B, long long V,
                         unsigned long long* out3b, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
+ * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
+ * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
+ * (eps 1e-12); s_bij = <x_bi, x_bj> / tau; mask: (B, N) float, the pair is positive when mask[b,i] == mask[b,j] (the diagonal
+ * included), negative otherwise; all B*N^2 ordered pairs, pooled over the batch.  Binning is np.histogram(values_f32, bins)'s:
+ * range = float32 (min, max), +-0.5 when equal, (0, 1) when the set is empty; edge[k] = k*step + lo in float32 (no fma),
+ * edge[bins] = hi.  Outputs (device): counts[2][bins] (pos, neg), edges[2][bins+1], minmax = pos lo, hi, neg lo, hi (the sets'
+ * float32 extremes; 0, 1 for an empty set).  1 <= bins <= 256.  Bitwise reproducible; workspace O(B*N). */
+size_t dycon_simhist_workspace(int B, int N, int Dm, int bins);
+int dycon_simhist(const void* feat, const float* mask, int dtype, int B, int N, int Dm, float tau, int bins,
+                  long long* counts, float* edges, float* minmax, float* workspace, size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
