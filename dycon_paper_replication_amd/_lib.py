@@ -103,6 +103,13 @@ SIGNATURES = {
     "dycon_batch_overlap": (I, [P, P, I, I, L, P, P]),
     "dycon_simhist_workspace": (Z, [I, I, I, I]),
     "dycon_simhist": (I, [P, P, I, I, I, I, F, I, P, P, P, P, Z, P]),
+    "dycon_tap_gather": (I, [P, P, I, I, I, I, I, I, P, I, P]),
+    "dycon_pack_wblocks": (I, [P, P, I, P, I, I, I, I, P, Z, I, P]),
+    "dycon_unpack_wgrad": (I, [P, L, I, P, P, P, I, I, I, P]),
+    "dycon_sample_colsum": (I, [P, I, P, I, L, I, F, I, P]),
+    "dycon_sample_bcast": (I, [P, P, P, I, I, L, I, F, P]),
+    "dycon_small_gemm": (I, [P, L, L, P, L, L, P, L, I, I, I, I, P]),
+    "dycon_copy_segments": (I, [P, P, P, I, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

@@ -108,20 +108,43 @@ def vnet_norm_sites(normalization="groupnorm"):
     return sites
 
 
+ASPP_BN_SITES = tuple(f"aspp.aspp{j}.bn" for j in range(1, 5)) + ("aspp.bn_after_pool", "aspp.bn1")
+
+
 def net_buffers(net_type, normalization="groupnorm", params=None):
-    """BatchNorm buffers of the net in state_dict order: the V-Net's own (normalization='batchnorm', VNet.py:17-18) + the head's."""
+    """BatchNorm buffers of the net in state_dict order: the V-Net's own (normalization='batchnorm', VNet.py:17-18), the U-Net's
+    ASPP's (when `params` has it) + the head's."""
     bufs = OrderedDict()
     if net_type == "vnet" and normalization == "batchnorm":
         spec = params if params is not None else vnet_param_spec(normalization=normalization)
         for site in vnet_norm_sites(normalization):
             c = tuple(spec[site + ".weight"])
             bufs[site + ".running_mean"], bufs[site + ".running_var"], bufs[site + ".num_batches_tracked"] = c, c, ()
+    if net_type == "unet_3D" and params is not None and "aspp.conv1.weight" in params:
+        for site in ASPP_BN_SITES:
+            c = tuple(params[site + ".weight"])
+            bufs[site + ".running_mean"], bufs[site + ".running_var"], bufs[site + ".num_batches_tracked"] = c, c, ()
     bufs.update(projection_buffers())
     return bufs
 
 
-def unet_param_spec(in_ch=1, n_classes=2):
-    """UNet3D.__init__ registration order (UNet3D_contrastive.py:222-267), feature_scale=4."""
+def aspp_param_spec(spec, c=256):
+    """ASPP3D(c, c, output_stride=16) registration order (networks/assp.py:28-54); buffers: net_buffers"""
+    for j, k in ((1, 1), (2, 3), (3, 3), (4, 3)):
+        spec[f"aspp.aspp{j}.atrous_conv.weight"] = (c, c, k, k, k)
+        spec[f"aspp.aspp{j}.bn.weight"] = (c,)
+        spec[f"aspp.aspp{j}.bn.bias"] = (c,)
+    spec["aspp.global_avg_pool.1.weight"] = (c, c, 1, 1, 1)
+    spec["aspp.bn_after_pool.weight"] = (c,)
+    spec["aspp.bn_after_pool.bias"] = (c,)
+    spec["aspp.conv1.weight"] = (c, 5 * c, 1, 1, 1)
+    spec["aspp.bn1.weight"] = (c,)
+    spec["aspp.bn1.bias"] = (c,)
+
+
+def unet_param_spec(in_ch=1, n_classes=2, use_aspp=False):
+    """UNet3D.__init__ registration order (UNet3D_contrastive.py:222-267), feature_scale=4; use_aspp: the ASPP's parameters
+    between out_conv2 and the projection head (UNet3D_contrastive.py:254-256)."""
     spec = OrderedDict()
     f = UNET_FILTERS
 
@@ -139,15 +162,19 @@ def unet_param_spec(in_ch=1, n_classes=2):
     spec["final.bias"] = (n_classes,)
     spec["out_conv2.weight"] = (n_classes, f[0], 1, 1, 1)
     spec["out_conv2.bias"] = (n_classes,)
+    if use_aspp:
+        aspp_param_spec(spec, f[4])
     _projection_spec(spec, f[4])
     return spec
 
 
-def param_spec(net_type, in_ch=1, n_classes=2, normalization="groupnorm"):
+def param_spec(net_type, in_ch=1, n_classes=2, normalization="groupnorm", use_aspp=False):
     if net_type == "vnet":
+        if use_aspp:
+            raise ValueError("use_aspp applies to the U-Net only (the reference's VNet takes no use_aspp)")
         return vnet_param_spec(in_ch, n_classes, normalization)
     if net_type == "unet_3D":
-        return unet_param_spec(in_ch, n_classes)
+        return unet_param_spec(in_ch, n_classes, use_aspp)
     raise ValueError(f"unknown net_type {net_type!r}")
 
 
@@ -157,7 +184,8 @@ class DropoutSpec:
 
     mode "off"    : identity (eval / parity runs with p = 0)
     mode "mask"   : explicit keep-masks in ``masks`` (parity tests feed the oracle's masks)
-                    V-Net keys "drop5", "drop9": (B, C) ; U-Net keys "drop_center", "drop_up1": NDHWC-shaped
+                    V-Net keys "drop5", "drop9": (B, C) ; U-Net keys "drop_center", "drop_up1", "drop_aspp" (ASPP output):
+                    NDHWC-shaped
     mode "philox" : on-device counter RNG, (seed, offset); offset must change every step
     """
 
@@ -176,6 +204,9 @@ class Engine:
         self.gen = 0                 # bump whenever parameter values change (invalidates packed weights)
         self._packed = {}
         self._jobs, self._jobs_dev, self._packed_gen = [], None, -1
+        self._xjobs = []             # block-table packs (ASPP, ops.pack_wblocks): (key, tables, KB, NB, kblk, nblk), refreshed by repack()
+        self.use_aspp = net_type == "unet_3D" and "aspp.conv1.weight" in params
+        self._aspp_plans = {}
         self._jobs_split, self._pack_event = False, None
         self.on_param_grads = None   # optional callback(name): called in backward once a layer's parameter gradients are enqueued
         self.wgrad_stream = None     # optional side stream for the weight-gradient launches of the backward (set by the trainer)
@@ -262,7 +293,7 @@ class Engine:
         `helper`, whose completion event the forward waits for right before the first layer that is not `early` (pack_ready).
         The 55 us pack of a V-Net then no longer stands in front of the step's first convolution."""
         self._pack_event = None
-        if not self._jobs or self._packed_gen == self.gen:
+        if (not self._jobs and not self._xjobs) or self._packed_gen == self.gen:
             return
         split = early is not None and helper is not None
         if self._jobs_dev is None or self._jobs_split != split:
@@ -279,16 +310,36 @@ class Engine:
             ops.fork(ops.cur_stream(), helper)       # the update that changed the parameters precedes this point
             with ops.on_stream(helper, light=True):
                 ops.pack_batch(d1, n1, b1)
+                self._repack_blocks()
                 ev1 = ops.Event()
                 ev1.record(helper)
             self._pack_event = ev1
         else:
             for d, n, b in self._jobs_dev:
                 ops.pack_batch(d, n, b)
+            self._repack_blocks()
         for key, _ in self._jobs:
             key = key[0] if isinstance(key[0], tuple) else key        # chunked packs register one job per chunk
             self._packed[key] = (self.gen, self._packed[key][1])
         self._packed_gen = self.gen
+
+    def _pk_blocks(self, key, tables, KB, NB, kblk, nblk, device):
+        """Packed block-table operand (ops.pack_wblocks) for ``key``: packed on the first request, refreshed by repack() (or lazily
+        here) whenever the parameters changed, like _pk."""
+        hit = self._packed.get(key)
+        if hit is not None and hit[0] == self.gen:
+            return hit[1]
+        buf = ops.pack_wblocks(tables, KB, NB, kblk, nblk, self.dtype, device, out=hit[1] if hit is not None else None)
+        if hit is None:
+            self._xjobs.append((key, tables, KB, NB, kblk, nblk))
+        self._packed[key] = (self.gen, buf)
+        return buf
+
+    def _repack_blocks(self):
+        for key, tables, KB, NB, kblk, nblk in self._xjobs:
+            buf = self._packed[key][1]
+            ops.pack_wblocks(tables, KB, NB, kblk, nblk, self.dtype, buf.device, out=buf)
+            self._packed[key] = (self.gen, buf)
 
     def pack_ready(self):
         """the packs launched on the helper stream by repack(early=..., helper=...) are needed from here on"""
@@ -706,9 +757,161 @@ class Engine:
             self.tape.append(bwd)
         return y
 
+    # ---------------------------------------------------------------- ASPP (feature branch)
+    def _aspp_tables(self, dhw):
+        """host tables of the ASPP at this bottleneck grid (TapPlan + the pointer tables of its packs and scatters), built once"""
+        key = tuple(dhw)
+        t = self._aspp_plans.get(key)
+        if t is None:
+            import ctypes as C
+            from .aspp import ASPP_BRANCHES, TapPlan
+            plan = TapPlan(dhw, ASPP_BRANCHES)
+            ws = [self.p[f"aspp.aspp{j}.atrous_conv.weight"] for j in range(1, 5)]
+            c = ws[0].shape[0]
+            t = {"plan": plan, "fwd": plan.fwd_tables(ws, c), "dgrad": plan.dgrad_tables(ws, c), "c": c, "gkey": None}
+            # the four branch BatchNorms run as ONE 4c-channel BatchNorm: gamma | beta | running mean | running var gathered
+            # into aff[0:4c] ... [12c:16c] (and the running statistics written back, the affine gradients scattered)
+            dev = ws[0].device
+            t["aff"] = aff = torch.empty(16 * c, dtype=torch.float32, device=dev)
+            t["dgb"] = dgb = torch.empty(8 * c, dtype=torch.float32, device=dev)
+            sites = [f"aspp.aspp{j}.bn" for j in range(1, 5)]
+
+            def segs(pairs):
+                return (ops.host_array(C.c_void_p, [a.data_ptr() for a, _ in pairs]),
+                        ops.host_array(C.c_void_p, [b.data_ptr() for _, b in pairs]),
+                        ops.host_array(C.c_int, [a.numel() for a, _ in pairs]), len(pairs))
+            gather = []
+            for q, leaf in enumerate((".weight", ".bias")):
+                gather += [(self.p[sj + leaf], aff[(4 * q + j) * c:(4 * q + j + 1) * c]) for j, sj in enumerate(sites)]
+            stats = []
+            if all(sj + ".running_mean" in self.buf for sj in sites):
+                for q, leaf in enumerate((".running_mean", ".running_var")):
+                    stats += [(self.buf[sj + leaf], aff[(8 + 4 * q + j) * c:(8 + 4 * q + j + 1) * c]) for j, sj in enumerate(sites)]
+            t["gather"] = segs(gather + stats)
+            if stats:
+                t["scatter_stats"] = segs([(b, a) for a, b in stats])
+            t["segs"] = segs
+            self._aspp_plans[key] = t
+        return t
+
+    def _aspp_grad_tables(self, t):
+        """pointer tables of the gradient writes (the module route hands the backward a fresh gradient dict each time)"""
+        wn = [f"aspp.aspp{j}.atrous_conv.weight" for j in range(1, 5)]
+        bn = [f"aspp.aspp{j}.bn{leaf}" for leaf in (".weight", ".bias") for j in range(1, 5)]
+        gs = [self.g[n] for n in wn + bn]
+        key = tuple(g.data_ptr() for g in gs)
+        if t["gkey"] != key:
+            c, dgb = t["c"], t["dgb"]
+            t["unpack"] = t["plan"].unpack_tables(gs[:4])
+            t["scatter_dgb"] = t["segs"]([(dgb[i * c:(i + 1) * c], g) for i, g in enumerate(gs[4:])])
+            t["gkey"] = key
+
+    def _aspp(self, x, training):
+        """ASPP3D (networks/assp.py:56-73) on the bottleneck: four dilated branches + the pool branch -> cat -> conv1 -> bn1 -> ReLU
+        -> Dropout(0.5).  The branches are one GEMM over their live taps (aspp.TapPlan) writing one (.., 4c) tensor, normalised by
+        one BatchNorm launch; the pool branch is constant over space, so its share of conv1 is a per-sample bias and the
+        (.., 5c) concatenation is never formed."""
+        B, d, h, w, c = x.shape
+        V, M = d * h * w, B * d * h * w
+        t = self._aspp_tables((d, h, w))
+        plan, NB = t["plan"], 4
+        N = NB * c
+        dev, f32 = x.device, dict(dtype=torch.float32, device=x.device)
+        upd = training and self.update_bn
+        # -- spatial branches: one GEMM (K = live offsets x c, N = 4c), one 4c-channel BatchNorm + ReLU
+        wf = self._pk_blocks(("aspp", "f", (d, h, w)), t["fwd"], plan.KB, NB, c, c, dev)
+        a = x if plan.KB == 1 else ops.tap_gather(x, plan.taps_host, plan.KB)
+        z = ops.conv_gemm(a, wf, None, CONV_1X1, N, N)
+        aff = t["aff"]
+        ops.copy_segments(t["gather"])
+        gam, bet, rm, rv = aff[:N], aff[N:2 * N], aff[2 * N:3 * N], aff[3 * N:]
+        if training:
+            ybr, st = ops.norm_fwd(z, 1, M, N, N, gam, bet, True, None, None, 1e-5, rm if upd else None, rv if upd else None, 0.1)
+            if upd and "scatter_stats" in t:
+                ops.copy_segments(t["scatter_stats"])
+                for j in range(1, 5):
+                    nbt = self.buf.get(f"aspp.aspp{j}.bn.num_batches_tracked")
+                    if nbt is not None:
+                        ops.rec(lambda nbt=nbt: nbt.add_(1))
+        else:
+            st = torch.stack([rm, torch.rsqrt(rv + 1e-5)], 1).reshape(-1).contiguous()
+            ybr = ops.norm_apply(z, st, 1, M, N, N, gam, bet, True)
+        # -- pool branch (B, c): mean -> 1x1 -> [BN if B > 1] -> ReLU, then its share of conv1 as a per-sample bias
+        wp, wc1 = self.p["aspp.global_avg_pool.1.weight"], self.p["aspp.conv1.weight"]
+        wc1_pool = wc1.reshape(-1)[N:]
+        v = ops.sample_colsum(x, torch.empty((B, c), **f32), 1.0 / V)
+        zp = ops.small_gemm(v, 1, c, wp, 1, c, torch.empty((B, c), **f32), c, B, c, c)
+        pool_bn = B > 1       # assp.py:66-67: bn_after_pool only for more than one sample, in train and eval mode alike
+        if pool_bn:
+            pg, pb_ = self.p["aspp.bn_after_pool.weight"], self.p["aspp.bn_after_pool.bias"]
+            prm, prv = self.buf.get("aspp.bn_after_pool.running_mean"), self.buf.get("aspp.bn_after_pool.running_var")
+            if training:
+                pv, pst = ops.norm_fwd(zp, 1, B, c, c, pg, pb_, True, None, None, 1e-5, prm if upd else None, prv if upd else None, 0.1)
+                nbt = self.buf.get("aspp.bn_after_pool.num_batches_tracked")
+                if upd and nbt is not None:
+                    ops.rec(lambda: nbt.add_(1))
+            else:
+                pst = torch.stack([prm, torch.rsqrt(prv + 1e-5)], 1).reshape(-1).contiguous()
+                pv = ops.norm_apply(zp, pst, 1, B, c, c, pg, pb_, True)
+        else:
+            pv = ops.relu_fwd(zp)
+        bias = ops.small_gemm(pv, 1, c, wc1_pool, 1, 5 * c, torch.empty((B, c), **f32), c, B, c, c)
+        # -- conv1 over the four spatial branches (+ the pool branch's bias)
+        wc1f = self._pk(("aspp.conv1", "f"), "frag", wc1, 1, N, c, c, 0, 1, 0, 5 * c)
+        z1 = ops.conv_gemm(ybr, wc1f, None, CONV_1X1, c, c)
+        ops.sample_bcast(z1, bias, z1)
+        if self.recording:
+            def bwd():
+                gz1 = self._take(z1)
+                g = self.g
+                # bn1's backward may have left its dgamma / dbeta sum pending (defer_dparams): add it up here, on this branch's
+                # stream -- the next convolution to flush it would be the decoder's, on a stream that does not wait for this one
+                self._flush_dparams()
+                self._aspp_grad_tables(t)
+                # conv1: data gradient to the four branches, weight gradient of its first 4c input channels
+                wc1d = self._pk(("aspp.conv1", "d"), "frag", wc1, 1, c, N, N, 0, 5 * c, 0, 1)
+                gbr = ops.conv_gemm(gz1, wc1d, None, CONV_1X1, N, N)
+                ops.conv_wgrad(ybr, gz1, g["aspp.conv1.weight"], CONV_1X1, 0, 1, 5 * c)
+                # pool branch: its bias gradient is the per-sample column sum of gz1
+                gbias = ops.sample_colsum(gz1, torch.empty((B, c), **f32), 1.0)
+                gw1p = g["aspp.conv1.weight"].reshape(-1)[N:]
+                ops.small_gemm(gbias, c, 1, pv, c, 1, gw1p, 5 * c, c, c, B)
+                gpv = ops.small_gemm(gbias, 1, c, wc1_pool, 5 * c, 1, torch.empty((B, c), **f32), c, B, c, c)
+                if pool_bn:
+                    gzp = ops.norm_bwd(zp, False, gpv, pst, 1, B, c, c, pg, pb_, True, g["aspp.bn_after_pool.weight"],
+                                       g["aspp.bn_after_pool.bias"])
+                else:
+                    gzp = ops.relu_bwd(zp, gpv)
+                ops.small_gemm(gzp, c, 1, v, c, 1, g["aspp.global_avg_pool.1.weight"], c, c, c, B)
+                gv = ops.small_gemm(gzp, 1, c, wp, c, 1, torch.empty((B, c), **f32), c, B, c, c)
+                # the four branches: BatchNorm backward (one launch), weight gradients (one GEMM + unpack), data gradient
+                dgb = t["dgb"]
+                gz = ops.norm_bwd(z, False, gbr, st, 1, M, N, N, gam, bet, True, dgb[:N], dgb[N:])
+                ops.copy_segments(t["scatter_dgb"])
+                dense = torch.empty(plan.KB * c * N, **f32)
+                ops.conv_wgrad(a, gz, dense, CONV_1X1, 0, N, 1)
+                ops.unpack_wgrad(dense, N, plan.KB, t["unpack"], c, c)
+                wd = self._pk_blocks(("aspp", "d", (d, h, w)), t["dgrad"], plan.KB * NB, 1, c, c, dev)
+                ag = gz if plan.KB == 1 else ops.tap_gather(gz, plan.neg_taps_host, plan.KB)
+                gx = ops.conv_gemm(ag, wd, None, CONV_1X1, c, c)
+                ops.sample_bcast(gx, gv, gx, 1.0 / V)          # + the pool's mean: g_v / V on every voxel
+                if self.on_param_grads is not None:
+                    names = ["aspp.bn1.weight", "aspp.conv1.weight"]
+                    names += (["aspp.bn_after_pool.weight"] if pool_bn else []) + ["aspp.global_avg_pool.1.weight"]
+                    for j in range(4, 0, -1):
+                        names += [f"aspp.aspp{j}.bn.weight", f"aspp.aspp{j}.atrous_conv.weight"]
+                    for n in names:
+                        self.on_param_grads(n)
+                self._give(x, gx)
+            self.tape.append(bwd)
+        y = self._norm("aspp.bn1", z1, "bn", relu=True, training=training)
+        return self._drop_elements(y, "drop_aspp", 0.5, 2)      # nn.Dropout(0.5), element-wise (assp.py:73)
+
     # ---------------------------------------------------------------- feature head
     def _head(self, center, training):
-        """UNet3D_contrastive.py:261-267, 308-310: trilinear x scale (align_corners=True) -> 1x1 -> BN -> ReLU -> 1x1 -> BN."""
+        """UNet3D_contrastive.py:261-267, 304-310: [ASPP ->] trilinear x scale (align_corners=True) -> 1x1 -> BN -> ReLU -> 1x1 -> BN."""
+        if self.use_aspp:
+            center = self._aspp(center, training)
         B, d, h, w, C = center.shape
         s = self.scale_factor
         c = ops.trilinear_fwd(center, (d * s, h * s, w * s), True)

@@ -86,13 +86,14 @@ class HipSegNet(nn.Module):
     net_type = None
 
     def __init__(self, in_channels=1, n_classes=2, scale_factor=2, normalization="groupnorm", has_dropout=True,
-                 dtype=torch.float32, seed=None):
+                 dtype=torch.float32, seed=None, use_aspp=False):
         super().__init__()
         if n_classes != 2:
             raise NotImplementedError("the DyCON step hard-codes 2 classes (train_DyCON_BraTS19.py:146)")
         self.in_channels, self.n_classes, self.scale_factor = in_channels, n_classes, scale_factor
         self.normalization, self.has_dropout, self.compute_dtype = normalization, has_dropout, dtype
-        spec = param_spec(self.net_type, in_channels, n_classes, normalization)
+        self.use_aspp = bool(use_aspp)
+        spec = param_spec(self.net_type, in_channels, n_classes, normalization, self.use_aspp)
         self._param_names = list(spec)
         gen = torch.Generator().manual_seed(seed) if seed is not None else None
         for name, shape in spec.items():
@@ -111,14 +112,15 @@ class HipSegNet(nn.Module):
         self._drop_calls = 0
         self._drop_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
 
-    # kaiming-normal fan_in conv weights, BN gamma ~ N(1, 0.02), beta = 0 (networks_other.py:40-49);
+    # kaiming-normal fan_in conv weights, BN gamma ~ N(1, 0.02), beta = 0 (networks_other.py:40-49; the ASPP's BatchNorms too:
+    # UNet3D.__init__'s loop runs after build_aspp3d, UNet3D_contrastive.py:254-270);
     # conv biases / GroupNorm affine keep torch's defaults (uniform(+-1/sqrt(fan_in)), ones / zeros)
     @staticmethod
     def _init_tensor(name, shape, gen):
         if len(shape) == 5:
             fan_in = shape[1] * shape[2] * shape[3] * shape[4]
             return torch.randn(shape, generator=gen) * math.sqrt(2.0 / fan_in)
-        if name.startswith("projection.1.") or name.startswith("projection.4."):
+        if name.startswith("projection.1.") or name.startswith("projection.4.") or name.startswith("aspp."):
             return 1.0 + 0.02 * torch.randn(shape, generator=gen) if name.endswith("weight") else torch.zeros(shape)
         if name.endswith(".weight"):
             return torch.ones(shape)

@@ -791,6 +791,77 @@ def similarity_histograms(feat, mask, tau=0.6, bins=50):
     return counts, edges, minmax
 
 
+# ------------------------------------------------------------------ ASPP (dilated convolutions over their live taps, pool branch)
+def host_array(ctype, values):
+    """A host array argument (a `_host` pointer of the C ABI).  The caller keeps it alive as long as a recorded step may re-issue
+    the call (the engine caches its tables); while a step is being recorded the recorder keeps it too."""
+    return (ctype * len(values))(*values)
+
+
+def _h(arr):
+    if _lib.RECORDER is not None:
+        _lib.RECORDER.keep.append(arr)
+    return arr
+
+
+def tap_gather(x, taps_host, ntaps, out=None):
+    """(B,D,H,W,C) -> (B,D,H,W,ntaps*C): x shifted by each (dz, dy, dx) of taps_host, zeros outside the grid"""
+    B, D, H, W, C = x.shape
+    if out is None:
+        out = torch.empty((B, D, H, W, ntaps * C), dtype=x.dtype, device=x.device)
+    with _Region("tap_gather", (x.numel() + out.numel()) * _es(x), 0):
+        call("dycon_tap_gather", _p(x), _p(out), dt(x), B, D, H, W, C, _h(taps_host), ntaps, _s())
+    return out
+
+
+def pack_wblocks(tables, KB, NB, kblk, nblk, dtype, device, out=None):
+    """MFMA B fragments of a block table (dycon_pack_wblocks); tables = (w_host, strides_host, nsrc, blk_host) host arrays"""
+    d = _DT[dtype]
+    nbytes = query("dycon_bfrag_bytes", d, 1, KB * kblk, NB * nblk)
+    if out is None:
+        out = torch.empty(nbytes // (2 if d == BF16 else 4), dtype=dtype, device=device)
+    w_host, strides_host, nsrc, blk_host = tables
+    call("dycon_pack_wblocks", _h(w_host), _h(strides_host), nsrc, _h(blk_host), KB, NB, kblk, nblk, _p(out), nbytes, d, _s())
+    return out
+
+
+def unpack_wgrad(dense, ldd, KB, tables, Ci, Co):
+    """dense fp32 [KB*Ci][ldd] -> the branches' (Co, Ci, k, k, k) weight gradients, zeros on pruned taps"""
+    g_host, taps_host, kb_host, ndst = tables
+    call("dycon_unpack_wgrad", _p(dense), ldd, KB, _h(g_host), _h(taps_host), _h(kb_host), ndst, Ci, Co, _s())
+
+
+def sample_colsum(x, out, scale=1.0, accumulate=False):
+    """out (B, C) fp32 (+)= scale * sum over the voxels of each sample of x (B, ..., C)"""
+    B, C = x.shape[0], x.shape[-1]
+    V = x.numel() // (B * C)
+    with _Region("sample_colsum", x.numel() * _es(x), x.numel()):
+        call("dycon_sample_colsum", _p(x), dt(x), _p(out), B, V, C, float(scale), int(accumulate), _s())
+    return out
+
+
+def sample_bcast(x, vec, out, scale=1.0):
+    """out[b, v, c] = (x[b, v, c] if x is not None else 0) + scale * vec[b, c]; x may be out"""
+    B, C = out.shape[0], out.shape[-1]
+    V = out.numel() // (B * C)
+    with _Region("sample_bcast", out.numel() * _es(out) * (3 if x is not None else 1), out.numel()):
+        call("dycon_sample_bcast", _p(x), _p(vec), _p(out), dt(out), B, V, C, float(scale), _s())
+    return out
+
+
+def small_gemm(a, sar, sai, b, sbr, sbj, c, ldc, I, J, R, accumulate=False):
+    """c[i*ldc + j] (+)= sum_r a[r*sar + i*sai] * b[r*sbr + j*sbj]   (fp32, flat contiguous views)"""
+    with _Region("small_gemm", 0, 2 * I * J * R):
+        call("dycon_small_gemm", _p(a), sar, sai, _p(b), sbr, sbj, _p(c), ldc, I, J, R, int(accumulate), _s())
+    return c
+
+
+def copy_segments(tables):
+    """tables = (src_host, dst_host, n_host, nseg): dst[k][:n] = src[k][:n]"""
+    src_host, dst_host, n_host, nseg = tables
+    call("dycon_copy_segments", _h(src_host), _h(dst_host), _h(n_host), nseg, _s())
+
+
 # ------------------------------------------------------------------ optimiser
 def sumsq(g, out):
     call("dycon_sumsq", _p(g), g.numel(), _p(out), _s())

@@ -36,6 +36,7 @@ from .utils.dycon_losses import adaptive_beta, sigmoid_rampup
 class TrainConfig:
     """Flag names and defaults of code/train_DyCON_BraTS19.py:26-67."""
     model: str = "vnet"                 # "vnet" | "unet_3D"
+    use_aspp: bool = False              # unet_3D: ASPP3D before the projection head (net_factory_3d(use_aspp=True))
     normalization: str = "groupnorm"    # V-Net only
     max_iterations: int = 20000
     batch_size: int = 8                 # per process
@@ -118,7 +119,7 @@ class DyconTrainer:
         # the data-parallel exchange (bucketed gradient all-reduce, 16 + 4-double loss exchange); ddp_force runs it with ONE rank too,
         # where every collective is the identity (tests: the RCCL calls inside the recorded step, on the single GPU of a test box)
         self.ddp = self.world > 1 or (cfg.ddp_force and process_group is not None)
-        spec = param_spec(cfg.model, 1, 2, cfg.normalization)
+        spec = param_spec(cfg.model, 1, 2, cfg.normalization, cfg.use_aspp)
         # parameters the loss never reaches keep grad=None in the reference and are skipped by
         # clip_grad_norm_/SGD (weight decay included): put them behind the SGD range of the arena
         nograd = [k for k in spec if k.startswith("final.")]
@@ -146,8 +147,10 @@ class DyconTrainer:
         self.g = OrderedDict((k, view(self.flat_g, k)) for k in spec)
 
         # nn.Module shells (state_dict / eval-mode inference); their parameters alias the arenas
-        self.model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, dtype=cfg.dtype, normalization=cfg.normalization)
-        self.ema_model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, dtype=cfg.dtype, normalization=cfg.normalization)
+        self.model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
+                                    normalization=cfg.normalization)
+        self.ema_model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
+                                        normalization=cfg.normalization)
         g0 = torch.Generator().manual_seed(cfg.seed)
         for mod, init, arena in ((self.model, student_init, self.p), (self.ema_model, teacher_init, self.t)):
             if init is None:     # two independently initialised nets, as create_model() x2 (:212-230); same on every rank

@@ -431,6 +431,39 @@ size_t dycon_simhist_workspace(int B, int N, int Dm, int bins);
 int dycon_simhist(const void* feat, const float* mask, int dtype, int B, int N, int Dm, float tau, int bins,
                   long long* counts, float* edges, float* minmax, float* workspace, size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- 3-D ASPP (networks/assp.py:28-82; UNet3D(use_aspp=True))
+ * The dilated k=3 convolutions run on dycon_conv_gemm (1x1 mode) over their live taps only: per axis of extent n the offsets +-d
+ * can read data only if d < n (the caller plans the taps from the shape); their data gradient gathers the output gradient at
+ * the negated offsets.  taps_host: ntaps (dz, dy, dx) triples, host memory.
+ *   dycon_tap_gather : y (B,D,H,W, ntaps*C) = x shifted by each tap (zero outside the grid); C % 8 (bf16) / % 4 (f32) == 0
+ *   dycon_pack_wblocks: MFMA B fragments (dycon_pack_bfrag order, T = 1, Cin = KB*kblk, N = NB*nblk) of a block table:
+ *       block (kb, nb) = blk_host[kb*NB + nb] = src*32 + tap (or -1: zeros), element (k, n) of a block =
+ *       w_host[src][tap + (k % kblk) * strides_host[2*src] + (n % nblk) * strides_host[2*src+1]]  (w_host: device pointers)
+ *   dycon_unpack_wgrad: dense fp32 [KB*Ci][ldd] (column j*Co + co) -> g_host[j] (Co, Ci, taps_host[j] in {1, 27}) with
+ *       g[co][ci][tap] = dense[(kb_host[j*27 + tap] * Ci + ci) * ldd + j*Co + co], or 0 where kb_host is -1 (pruned taps)
+ *   dycon_sample_colsum: out[b][c] (+)= scale * sum_v x[b][v][c]      (global average pool; per-sample bias gradient)
+ *   dycon_sample_bcast : y[b][v][c] = (x ? x[b][v][c] : 0) + scale * vec[b][c]   (x may alias y)
+ *   dycon_small_gemm   : c[i*ldc + j] (+)= sum_r a[r*sar + i*sai] * b[r*sbr + j*sbj], fp32, r in order (pool-branch products)
+ *   dycon_copy_segments: dst_host[k][0..n_host[k]) = src_host[k][...] for nseg <= DYCON_SEGS_MAX fp32 segments (device pointers)
+ * All reject bad arguments before any launch and are bitwise reproducible. */
+#define DYCON_TAPS_MAX 64
+#define DYCON_WBLK_SRC_MAX 8
+#define DYCON_WBLK_MAX 512
+#define DYCON_SEGS_MAX 16
+int dycon_tap_gather(const void* x, void* y, int dtype, int B, int D, int H, int W, int C, const int* taps_host, int ntaps,
+                     dycon_stream_t stream);
+int dycon_pack_wblocks(const float* const* w_host, const long long* strides_host, int nsrc, const short* blk_host, int KB, int NB,
+                       int kblk, int nblk, void* out, size_t out_bytes, int dtype, dycon_stream_t stream);
+int dycon_unpack_wgrad(const float* dense, long long ldd, int KB, float* const* g_host, const int* taps_host, const short* kb_host,
+                       int ndst, int Ci, int Co, dycon_stream_t stream);
+int dycon_sample_colsum(const void* x, int dtype, float* out, int B, long long V, int C, float scale, int accumulate,
+                        dycon_stream_t stream);
+int dycon_sample_bcast(const void* x, const float* vec, void* y, int dtype, int B, long long V, int C, float scale,
+                       dycon_stream_t stream);
+int dycon_small_gemm(const float* a, long long sar, long long sai, const float* b, long long sbr, long long sbj, float* c,
+                     long long ldc, int I, int J, int R, int accumulate, dycon_stream_t stream);
+int dycon_copy_segments(const float* const* src_host, float* const* dst_host, const int* n_host, int nseg, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
