@@ -946,6 +946,13 @@ class Engine:
         return feats
 
     # ---------------------------------------------------------------- V-Net
+    def _fuses_first_block(self, x, nk, training):
+        """whether the V-Net's block_one runs as _first_block: bf16, a normalisation with batch statistics, the 1 -> 16 layer, and at
+        most 16 samples (dycon_first_block_bwd refuses more)"""
+        w1 = self.p["block_one.conv.0.weight"]
+        return (self.fuse_first and self.dtype == torch.bfloat16 and nk != "none" and not (nk == "bn" and not training)
+                and w1.shape[0] == 16 and w1.shape[1] == 1 and x.shape[0] <= 16)
+
     def _vnet(self, x, training):
         nk = {"groupnorm": "gn", "instancenorm": "in", "batchnorm": "bn", "none": "none"}[self.normalization]
         st = 2 if nk == "none" else 3       # nn.Sequential index step: conv, [norm,] relu
@@ -969,9 +976,7 @@ class Engine:
         def up(name, t, skip):
             return self._norm(f"{name}.conv.1", self._conv(f"{name}.conv.0", t, "deconv"), nk, skip=skip, training=training)
 
-        w1 = self.p["block_one.conv.0.weight"]
-        if (self.fuse_first and self.dtype == torch.bfloat16 and nk != "none" and not (nk == "bn" and not training)
-                and w1.shape[0] == 16 and w1.shape[1] == 1 and x.shape[0] <= 16):
+        if self._fuses_first_block(x, nk, training):
             x1 = self._first_block("block_one", x, nk, training)
         else:
             x1 = block("block_one", x, 1, first=True)

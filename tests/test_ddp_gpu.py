@@ -129,6 +129,7 @@ def test_two_rank_step_with_fecl_vs_ddp_oracle():
             gr = torch.cat([ref["grads"][k].reshape(-1) for k in ref["grads"]])
             cos = float((gh * gr).sum() / (gh.norm() * gr.norm()))
             for k, g64 in ref["grads"].items():
+                assert bool(torch.isfinite(got["g0"][k]).all()), f"{k}: averaged gradient holds NaN / Inf"   # (max() keeps 0.0 over a NaN)
                 nrm = float(g64.norm()) + 1e-30
                 if nrm > 1e-6 * float(ref["grad_norm"]):      # (analytically zero gradients hold round-off only)
                     worst_h = max(worst_h, float((got["g0"][k].double() - g64).norm()) / nrm)

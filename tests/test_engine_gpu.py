@@ -127,6 +127,9 @@ def test_full_net_fp32_vs_reference(kind):
             assert not ref.any() and torch.isnan(eng.g[k]).all()   # no gradient reaches the discarded sdf head
             continue
         got = _stats(eng.g[k])
+        # build() fills every gradient with NaN: a gradient the backward never wrote has NaN statistics, and a NaN would compare
+        # False with the running worst below and drop out of the comparison
+        assert np.isfinite(got).all(), f"{k}: gradient statistics {got} are not finite (never written, or NaN / Inf in the backward)"
         w = k[:-4] + "weight"
         one_channel_groups = kind == "unet" or eng.p[k].shape[0] == 16 or k.startswith("projection.")
         if k.endswith(".bias") and eng.p[w].dim() == 5 and not k.startswith("out_conv") and one_channel_groups:

@@ -36,8 +36,14 @@ BF = torch.bfloat16
 
 def assert_bf16_elementwise(got, ref, what, acc_noise=1e-3):
     """every element of a bf16-stored result within bf16 rounding (2^-8 relative, doubled) of the fp32 reference, plus fp32
-    accumulation-order noise `acc_noise` x rms(ref).  Reports the worst 4x8x8 voxel tile on failure."""
+    accumulation-order noise `acc_noise` x rms(ref).  Reports the worst 4x8x8 voxel tile on failure.  The reference must be finite
+    and the result may hold no NaN / Inf (it would compare False with the bound and pass)."""
     got, ref = got.float(), ref.float()
+    assert bool(torch.isfinite(ref).all()), f"{what}: the reference holds {int((~torch.isfinite(ref)).sum())} non-finite elements"
+    bad_f = ~torch.isfinite(got)
+    if bool(bad_f.any()):        # (a NaN compares False with every bound: it must be caught before the bound is taken)
+        idx = np.unravel_index(int(bad_f.reshape(-1).nonzero()[0, 0]), got.shape)
+        raise AssertionError(f"{what}: {int(bad_f.sum())} of {got.numel()} elements are NaN / Inf, first at {idx}")
     rms = float(ref.pow(2).mean().sqrt())
     excess = (got - ref).abs() - (2.0 ** -7) * ref.abs() - acc_noise * rms
     worst = float(excess.max())
