@@ -297,9 +297,6 @@ constexpr int CT_OS = CT_BN + 4;                            // fp32 row stride o
 // has 1935 SALU + 1158 VALU instructions per wave against 216 MFMAs, the matrix pipe busy 8.5 % of a wave's life and 42 % of it spent
 // in s_waitcnt / s_barrier.  KS2 = 2 (Cin % 64 == 0: the V-Net's 128- and 256-channel levels) halves the number of steps: 16 MFMAs
 // per barrier, two chunks of the same tap requested with one address computation (LDS 52 KB per workgroup: 3 per CU).
-#ifndef CT_DIAG
-#define CT_DIAG 0     // timing diagnostics only (wrong results): 1 no A loads, 2 no B loads, 4 no slab stores, 8 no MFMAs (bit mask)
-#endif
 template <int KS2>
 __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf,
                                                            const float* __restrict__ bias, bf16* __restrict__ Y,
@@ -354,11 +351,9 @@ __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(con
 #pragma unroll
         for (int u = 0; u < KS2; ++u) {                          // the chunks of a step share the tap: channels c + 32 u
             st.a[u] = make_uint4(0, 0, 0, 0);
-            if (!(CT_DIAG & 1) && in && kreq + u < kc1) st.a[u] = *reinterpret_cast<const uint4*>(xs + aoff + 64 * u);
-            if (!(CT_DIAG & 2) || kreq == kc0) {
-                st.b0[u] = *reinterpret_cast<const uint4*>(ws + (long long)u * NT * 1024 + boff);
-                st.b1[u] = *reinterpret_cast<const uint4*>(ws + (long long)u * NT * 1024 + boff + 4096);
-            }
+            if (in && kreq + u < kc1) st.a[u] = *reinterpret_cast<const uint4*>(xs + aoff + 64 * u);
+            st.b0[u] = *reinterpret_cast<const uint4*>(ws + (long long)u * NT * 1024 + boff);
+            st.b1[u] = *reinterpret_cast<const uint4*>(ws + (long long)u * NT * 1024 + boff + 4096);
         }
         kreq += KS2;
         c += 32 * KS2;
@@ -390,10 +385,7 @@ __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(con
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (CT_DIAG & 8) acc[m][j][0] += (float)a[m][0] * (float)b[j][0];
-                    else acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], b[j], acc[m][j], 0, 0, 0);
-                }
+                for (int j = 0; j < 4; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[m], b[j], acc[m][j], 0, 0, 0);
         }
     };
 
@@ -428,13 +420,12 @@ __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(con
 #pragma unroll
         for (int e = threadIdx.x; e < CT_BM * (CT_BN / 4); e += 256) {
             const int row = e / (CT_BN / 4), pc = e % (CT_BN / 4);
-            if (row < rows && !(CT_DIAG & 4))
+            if (row < rows)
                 *reinterpret_cast<float4*>(sl + (long long)row * N + pc * 4) = *reinterpret_cast<const float4*>(Ot + row * CT_OS + pc * 4);
         }
         return;
     }
-    if (slab) {                                                // span_major 1: span-major slabs (finish deferred to the one-launch norm); 2: the
-                                                               // lane-per-element row-major epilogue (DYCON_TILE_LDS_EPI=0, kept for A/B timing)
+    if (slab) {                                                // span_major 1: span-major slabs (finish deferred to the one-launch norm)
         float* sl = slab + (long long)blockIdx.z * M * N;
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -445,7 +436,7 @@ __global__ __launch_bounds__(256, KS2 == 1 ? 4 : 3) void conv_k3_tile_kernel(con
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int n = (nt0 + wn * 4 + j) * 16 + r;
-                    if (n < N) sl[span_major == 1 ? ((long long)(n >> 3) * M + mo) * 8 + (n & 7) : mo * N + n] = acc[m][j][i];
+                    if (n < N) sl[((long long)(n >> 3) * M + mo) * 8 + (n & 7)] = acc[m][j][i];
                 }
             }
         return;
@@ -639,17 +630,11 @@ constexpr int CL_HZ = CL_TZ + 2, CL_HY = CL_TY + 2, CL_HX = CL_TX + 2;
 constexpr int CL_NH = CL_HZ * CL_HY * CL_HX;     // 600 halo voxels
 constexpr int CL_NV = CL_TZ * CL_TY * CL_TX;     // 256 voxels = 16 m-tiles
 
-#ifndef CL_LB2
-#define CL_LB2 2                                   // min workgroups per CU the register allocation must allow: every variant fits 2 (<32,4,2>: 248 VGPRs, no scratch)
-#endif
-#ifndef CL_NTB64
-#define CL_NTB64 4                                 // n-tiles per workgroup for 64-wide output blocks (experiments: 2)
-#endif
-#ifndef CL_BPREF
-#define CL_BPREF 0                                 // B fragments read one k-step ahead of their MFMAs
-#endif
-template <int CK, int NTB, int WM, int NW = 4>     // NW waves per workgroup: 4, or 8 (two per SIMD) where the grid gives a CU one workgroup
-__global__ __launch_bounds__(64 * NW, NW == 4 ? CL_LB2 : 1) void conv_k3_lds_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf,
+constexpr int CL_NTB64 = 4;                        // n-tiles per workgroup for 64-wide output blocks
+// NW waves per workgroup: 4, or 8 (two per SIMD) where the grid gives a CU one workgroup.  With 4 waves the register allocation must
+// allow 2 workgroups per CU: every variant fits (<32,4,2>: 248 VGPRs, no scratch).
+template <int CK, int NTB, int WM, int NW = 4>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void conv_k3_lds_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf,
                                                           const float* __restrict__ bias, bf16* __restrict__ Y, int B, int D, int H,
                                                           int W, int Cin, int Cout, int NT, int tilesZ, int tilesY, int tilesX,
                                                           int accumulate) {
@@ -783,28 +768,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? CL_LB2 : 1) void conv_k3_lds_ker
 #pragma unroll
             for (int m = 0; m < MTW; ++m) afr[0][m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Xh + vbase[m] + toff));
         }
-#if CL_BPREF
-        bf16x8 bfr[2][NTW];
-#pragma unroll
-        for (int j = 0; j < NTW; ++j)
-            bfr[0][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Bs + ((wn * NTW + j) * 64 + lane) * 8));
-#pragma unroll
-        for (int u = 0; u < GRP; ++u) {
-            if (u + 1 < GRP) {
-                const int toff = tap_off(g * GRP + u + 1);
-#pragma unroll
-                for (int j = 0; j < NTW; ++j)
-                    bfr[(u + 1) & 1][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Bs + (((u + 1) * NTB + wn * NTW + j) * 64 + lane) * 8));
-#pragma unroll
-                for (int m = 0; m < MTW; ++m)
-                    afr[(u + 1) & 1][m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Xh + vbase[m] + toff));
-            }
-#pragma unroll
-            for (int m = 0; m < MTW; ++m)
-#pragma unroll
-                for (int j = 0; j < NTW; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[u & 1][m], bfr[u & 1][j], acc[m][j], 0, 0, 0);
-        }
-#else
 #pragma unroll
         for (int u = 0; u < GRP; ++u) {
             bf16x8 bfr[NTW];
@@ -822,7 +785,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? CL_LB2 : 1) void conv_k3_lds_ker
 #pragma unroll
                 for (int j = 0; j < NTW; ++j) acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[u & 1][m], bfr[j], acc[m][j], 0, 0, 0);
         }
-#endif
         if (has_next) {
             __syncthreads();                 // phase p fully consumed
             store_b();
@@ -921,12 +883,8 @@ struct TileStats {
 
 constexpr int P16_RP = 16;                                  // x-row pitch of the halo image in voxels (conflict-free, see above)
 constexpr int P16_XH = CL_HZ * CL_HY * P16_RP * 16;         // halo image, bf16 elements (30 KB)
-#ifndef P16_WGS
-#define P16_WGS 2                                            // workgroups per CU (register budget 256 VGPRs)
-#endif
-#ifndef P16_DEPTH
-#define P16_DEPTH 2                                          // halo tiles in flight per workgroup
-#endif
+constexpr int P16_WGS = 2;                                  // workgroups per CU (register budget 256 VGPRs)
+constexpr int P16_DEPTH = 2;                                // halo tiles in flight per workgroup
 
 // tiles of this workgroup: its XCD's contiguous range (workgroups are dealt to XCDs round-robin), walked with stride gridDim.x/8
 __device__ __forceinline__ void xcd_tile_range(int nTiles, int& first, int& end, int& stride) {
@@ -1167,18 +1125,6 @@ constexpr int P32_VS = 32;                                   // LDS voxel stride
 constexpr int P32_RP = CL_HX;                                // x-row pitch in voxels
 constexpr int P32_XH = CL_HZ * CL_HY * P32_RP * P32_VS;      // one halo image, bf16 elements (38.4 KB)
 constexpr int P32_BS = 27 * 2 * 64 * 8;                      // packed weights [tap][n-tile][lane][8] (55.3 KB)
-#ifndef P32_LA
-#define P32_LA 2                                             // LDS fragment reads run this many taps ahead of their MFMAs
-#endif
-#ifndef P32_BREG
-#define P32_BREG 0                                           // 1: all 54 weight fragments in registers instead of LDS (measured: 32.8 vs 30.5 us)
-#endif
-#ifndef P32_SGB
-#define P32_SGB 2                                            // VALU instructions requested between consecutive MFMAs (0: the compiler's order)
-#endif
-#ifndef P32_PIN
-#define P32_PIN 1                                            // halo pieces pinned inside their taps (0: the compiler places them)
-#endif
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -1190,14 +1136,6 @@ __device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {             
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
 }
 
-#ifdef P32_STAMP       // diagnostic builds only (tools/p32_stamps.py): where workgroup 0 / wave 0 spends its cycles, summed over its tiles
-__device__ unsigned long long p32_stamps[8];
-#define P32_T(var) unsigned long long var; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory"); __builtin_amdgcn_sched_barrier(0)
-extern "C" int dycon_debug_p32_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(p32_stamps), sizeof(p32_stamps)); }
-#else
-#define P32_T(var)
-#endif
-
 struct P32Geo {             // wave-uniform description of one tile
     long long org;          // element offset of voxel (b, z0, y0, x0), 32 channels per voxel
     int z0, y0, x0;
@@ -1205,15 +1143,13 @@ struct P32Geo {             // wave-uniform description of one tile
     int b;                  // sample
 };
 
-template <int NW, bool STATS>      // NW waves per workgroup: 4 (one per SIMD) or 8 (two per SIMD: a single wave is vector-issue bound); STATS: stat_part
+template <int NW, bool STATS>      // NW waves per workgroup: launched with 8 (two per SIMD: a single wave is vector-issue bound); STATS: stat_part
 __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf,
                                                              const float* __restrict__ bias, bf16* __restrict__ Y, int B, int D,
                                                              int H, int W, int tilesZ, int tilesY, int tilesX, int nTiles,
                                                              float* __restrict__ stat_part) {
     __shared__ __attribute__((aligned(16))) unsigned short Xh[2 * P32_XH];
-#if !P32_BREG
     __shared__ __attribute__((aligned(16))) unsigned short Bs[P32_BS];
-#endif
     int tile, t_end, t_stride;
     xcd_tile_range(nTiles, tile, t_end, t_stride);
     // stat_part: per-(sample, workgroup) {sum, sum of squares} of the STORED (bf16) outputs per channel, [B][gridDim.x][32][2] -- the
@@ -1226,27 +1162,12 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32_kernel(const bf16* __r
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 15, kg = lane >> 4;
     const int zs = wave & 3, yh = wave >> 2;                 // this wave: z-slice zs, y rows [8 / YH * yh, ...)
-#ifdef P32_STAMP
-    unsigned long long seg[6] = {0, 0, 0, 0, 0, 0};
-    P32_T(k0);
-#endif
-#if P32_BREG
-    // weights: all 54 B fragments (27 taps x 2 n-tiles) stay in this wave's registers for the lifetime of the workgroup -- with one
-    // wave per SIMD the 512-entry register file has room, and the LDS array serves A fragments only (4 instead of 6 reads per tap)
-    bf16x8 bw[27][2];
-#pragma unroll
-    for (int t = 0; t < 27; ++t)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-            bw[t][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Wf + ((long long)(t * 2 + j) * 64 + lane) * 8));
-#else
     // weights: every piece of this thread in flight at once (the packed order IS the fragment order: a linear copy)
     constexpr int NWP = P32_BS / 8;                          // 3456 pieces of 16 B
     constexpr int NWS = (NWP + NTHR - 1) / NTHR;             // 14 (7) per thread
     uint4 wst[NWS];
 #pragma unroll
     for (int it = 0; it < NWS; ++it) wst[it] = *reinterpret_cast<const uint4*>(Wf + (long long)min((int)threadIdx.x + NTHR * it, NWP - 1) * 8);
-#endif
 
     // A fragments (the MFMA's B operand): wave w owns z-slice w of the tile, m-tile m = y rows 2m, 2m+1; k-step t = tap t, lane group
     // kg reads the 8-channel chunk kg of voxel (x + dx), which sits at rotated position (kg + hx) & 3 of that voxel's 64 bytes.
@@ -1343,28 +1264,23 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32_kernel(const bf16* __r
     // is pinned inside its tap (sched_barrier), so that its address arithmetic, its load issue or LDS write fills the
     // vector-issue slots the tap's 8 MFMAs leave free: with one wave per SIMD nothing else would.
     auto one_tile = [&](int cur, const P32Geo& gcur, const P32Geo& gst, const uint4 (&st)[NST], P32Geo& gld, uint4 (&ld)[NST], int buf) {
-        P32_T(t0);
         const unsigned short* xh = Xh + buf * P32_XH;
         unsigned short* xo = Xh + (buf ^ 1) * P32_XH;
         geometry(cur + 2 * t_stride, gld);                   // (past the end: the last tile again -- loaded and written, never used)
         f32x4 acc[MT][2];
 #pragma unroll
         for (int m = 0; m < MT; ++m) { acc[m][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[m][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-        constexpr int LA = P32_LA, RING = P32_LA + 1;        // fragments of tap t+LA are requested before the MFMAs of tap t
+        constexpr int LA = 2, RING = LA + 1;                 // fragments of tap t+LA are requested before the MFMAs of tap t
         bf16x8 afr[RING][MT];
-#if !P32_BREG
         bf16x8 bfr[RING][2];
-#endif
         auto fetch = [&](int n) {
             const int imm = ((n / 9) * CL_HY + (n / 3) % 3) * P32_RP * P32_VS;
 #pragma unroll
             for (int m = 0; m < MT; ++m)
                 afr[n % RING][m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xh + abase[n % 3] + imm + m * MSTEP));
-#if !P32_BREG
 #pragma unroll
             for (int j = 0; j < 2; ++j)
                 bfr[n % RING][j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Bs + bbase + (n * 2 + j) * 512));
-#endif
         };
 #pragma unroll
         for (int n = 0; n < LA; ++n) fetch(n);
@@ -1377,24 +1293,16 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32_kernel(const bf16* __r
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int j = 0; j < 2; ++j)   // transposed: D[cout 4 kg + i][voxel r]
-#if P32_BREG
-                    acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[t][j], afr[t % RING][m], acc[m][j], 0, 0, 0);
-#else
                     acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[t % RING][j], afr[t % RING][m], acc[m][j], 0, 0, 0);
-#endif
-#if P32_SGB      // ask for MFMA / LDS read / 2 VALU in turn: an in-order wave hides other work only in the 8 issue cycles an MFMA leaves free
+            // ask for MFMA / LDS read / 2 VALU in turn: an in-order wave hides other work only in the 8 issue cycles an MFMA leaves free
 #pragma unroll
             for (int gq = 0; gq < MT * 2; ++gq) {
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, P32_SGB, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
             }
-#endif
-#if P32_PIN
-            if (t < 2 * NST) __builtin_amdgcn_sched_barrier(0);
-#endif
+            if (t < 2 * NST) __builtin_amdgcn_sched_barrier(0);   // halo piece pinned inside its tap
         }
-        P32_T(t4);
         {
             bf16* yb = Y + gcur.org + obase;
             const bool zok = gcur.z0 + zs < D, xok = gcur.x0 + (r & 7) < W;
@@ -1416,280 +1324,7 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32_kernel(const bf16* __r
                 }
             }
         }
-        P32_T(t5);
         __syncthreads();                                     // this tile's image consumed, the next one complete
-        P32_T(t6);
-#ifdef P32_STAMP
-        seg[0] += t4 - t0; seg[3] += t5 - t4; seg[4] += t6 - t5;
-#endif
-    };
-
-    uint4 sa[NST], sb[NST];
-    P32Geo g0, g1, g2;
-    geometry(tile, g0);
-#pragma unroll
-    for (int it = 0; it < NST; ++it) load_piece(g0, it, sa);
-    geometry(tile + t_stride, g1);
-#pragma unroll
-    for (int it = 0; it < NST; ++it) load_piece(g1, it, sb);
-#if !P32_BREG
-#pragma unroll
-    for (int it = 0; it < NWS; ++it)
-        if ((int)threadIdx.x + NTHR * it < NWP) *reinterpret_cast<uint4*>(Bs + (threadIdx.x + NTHR * it) * 8) = wst[it];
-#endif
-#pragma unroll
-    for (int it = 0; it < NST; ++it) store_piece(g0, it, sa, Xh);
-    __syncthreads();
-#ifdef P32_STAMP
-    P32_T(k1);
-#endif
-    for (; tile < t_end; tile += 2 * t_stride) {             // tile j of this workgroup's sequence: image j % 2, store set (j+1) % 2
-        if (STATS && g0.b != stat_b) { if (stat_b >= 0) flush_stats(stat_b); stat_b = g0.b; }
-        one_tile(tile, g0, g1, sb, g2, sa, 0);               // computes g0, writes g1's halo (sb), requests g2 into sa
-        if (tile + t_stride >= t_end) break;                 // (uniform)
-        if (STATS && g1.b != stat_b) { flush_stats(stat_b); stat_b = g1.b; }
-        one_tile(tile + t_stride, g1, g2, sa, g0, sb, 1);    // computes g1, writes g2's halo (sa), requests the next g0 into sb
-        g1 = g0;                                             // rotate: the tile just requested is the one after the next
-        g0 = g2;
-        // after the swap: g0 = the tile to compute, whose halo is in image 0 -- its data travelled in sa; g1 = requested into sb
-    }
-    if (STATS && stat_b >= 0) flush_stats(stat_b);
-#ifdef P32_STAMP
-    P32_T(k2);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (int i = 0; i < 6; ++i) p32_stamps[i] = seg[i];
-        p32_stamps[6] = k1 - k0;
-        p32_stamps[7] = k2 - k1;
-    }
-#endif
-}
-
-// The same kernel on v_mfma_f32_32x32x16_bf16: conv_k3_p32_kernel's tap loop is vector-ISSUE bound (stamps: ~215
-// issue cycles per tap against 128 of MFMA at one wave per SIMD), and a 16x16x32 MFMA holds the SIMD's vector issue for 8 of its 16
-// cycles, a 32x32x16 for 8 of its 32 (MI355X_MICROARCH.md, cycle constants): per tap a wave issues 2 (4) MFMAs instead of 4 (8) for
-// the same 32 output channels x 32 (64) voxels, with the same number of ds_read_b128 (one weight and one activation fragment per
-// k-step of 16 channels).  Output tile = 32 channels x 32 voxels (4 y rows x 8 x): one accumulator of 16 registers per 32 voxels.
-// Differences to conv_k3_p32_kernel: fragment order of the weights in LDS (re-ordered in the prologue copy), rotation of the 8-channel
-// chunks inside a voxel's 64 bytes (conflict-free for the 32-voxel read pattern), epilogue lane map.  Same results bit for bit is NOT
-// expected (the k order inside a tap differs: two k-steps of 16 instead of one of 32): tested element-wise like every conv kernel.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-template <int NW, bool STATS>
-__global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32x_kernel(const bf16* __restrict__ X, const bf16* __restrict__ Wf,
-                                                             const float* __restrict__ bias, bf16* __restrict__ Y, int B, int D,
-                                                             int H, int W, int tilesZ, int tilesY, int tilesX, int nTiles,
-                                                             float* __restrict__ stat_part) {
-    __shared__ __attribute__((aligned(16))) unsigned short Xh[2 * P32_XH];
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[P32_BS];
-    int tile, t_end, t_stride;
-    xcd_tile_range(nTiles, tile, t_end, t_stride);
-    // stat_part: per-(sample, workgroup) {sum, sum of squares} of the STORED (bf16) outputs per channel, [B][gridDim.x][32][2] -- the
-    // statistics pass of the normalisation that follows (norm_partial_kernel) then does not run: a persistent workgroup adds up its ~7
-    // tiles in registers and writes one row per sample it touched (rows of the other samples: zero)
-    if (STATS && threadIdx.x < 64)
-        for (int n = 0; n < B; ++n) stat_part[((long long)n * gridDim.x + blockIdx.x) * 64 + threadIdx.x] = 0.f;
-    if (tile >= t_end) return;                               // (uniform)
-    constexpr int NTHR = 64 * NW, YH = NW / 4, NA = 2 / YH;   // y-halves of a z-slice over the waves; 32-voxel accumulators (4 y rows x 8) per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r5 = lane & 31, hl = lane >> 5;                // MFMA 32x32x16: column (voxel) r5, k half hl
-    const int zs = wave & 3, yh = wave >> 2;                 // this wave: z-slice zs, y rows [8 / YH * yh, ...)
-#ifdef P32_STAMP
-    unsigned long long seg[6] = {0, 0, 0, 0, 0, 0};
-    P32_T(k0);
-#endif
-    // weights: every piece of this thread in flight at once.  The packed order (dycon_pack_bfrag: [tap][16-column tile][lane of the
-    // 16x16x32 fragment][8]) is re-ordered on the way into LDS into the A fragments of the 32x32x16 instruction, [tap][k-step of 16
-    // channels][lane][8] with lane = (k half hl, output channel r5): a permutation of whole 16-byte pieces
-    constexpr int NWP = P32_BS / 8;                          // 3456 pieces of 16 B
-    constexpr int NWS = (NWP + NTHR - 1) / NTHR;             // 14 (7) per thread
-    uint4 wst[NWS];
-#pragma unroll
-    for (int it = 0; it < NWS; ++it) {
-        const int e = min((int)threadIdx.x + NTHR * it, NWP - 1);
-        const int tp = e >> 7, ks = (e >> 6) & 1, hh = (e >> 5) & 1, rr = e & 31;
-        const int src = tp * 128 + (rr >> 4) * 64 + ((2 * ks + hh) << 4) + (rr & 15);
-        wst[it] = *reinterpret_cast<const uint4*>(Wf + (long long)src * 8);
-    }
-
-    // Activation fragments (the MFMA's B operand, 16 channels x 32 voxels): wave w owns z-slice zs, accumulator a = y rows 4a .. 4a+3
-    // of its half; k-step ks of tap t reads the 8-channel chunk c = 2 ks + hl of voxel (y, x + dx), which sits at rotated position
-    // (c + ((x + dx) >> 1)) & 3 of that voxel's 64 bytes: the 16 lanes ds_read_b128 services together then hit 64 distinct banks
-    // (lane groups {0-3, 12-15, 20-27} ...: per 16-bank window the four voxels have x = w, w + 2, w + 4, w + 6 modulo 8).
-    constexpr int ASTEP = 4 * P32_RP * P32_VS;
-    int abase[3][2];
-    {
-        const int vb = ((zs * CL_HY + 4 * NA * yh + (r5 >> 3)) * P32_RP + (r5 & 7)) * P32_VS;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) abase[dx][ks] = vb + dx * P32_VS + 8 * ((2 * ks + hl + (((r5 & 7) + dx) >> 1)) & 3);
-    }
-    const int bbase = lane * 8;
-
-    constexpr int NPC = CL_NH * 4;                           // 2400 halo pieces of 16 B
-    constexpr int NST = (NPC + NTHR - 1) / NTHR;             // per thread (10 or 5; pieces past the end duplicate the last one)
-    int rel[NST], lofs[NST];
-    unsigned need[NST];
-#pragma unroll
-    for (int it = 0; it < NST; ++it) {
-        const int e = min((int)threadIdx.x + NTHR * it, NPC - 1);
-        const int hv = e >> 2, pc = e & 3;
-        const int hx = hv % CL_HX, hy = (hv / CL_HX) % CL_HY, hz = hv / (CL_HX * CL_HY);
-        rel[it] = (((hz - 1) * H + (hy - 1)) * W + (hx - 1)) * 32 + 8 * pc;
-        lofs[it] = ((hv / CL_HX) * P32_RP + hx) * P32_VS + 8 * ((pc + (hx >> 1)) & 3);
-        need[it] = (1u << hz) | (1u << (6 + hy)) | (1u << (16 + hx));
-    }
-    // output (C/D of 32x32x16): lane (r5, hl) holds, for its voxel r5 of each accumulator, channels 8 g + 4 hl + i  (register 4 g + i)
-    const int obase = ((zs * H + 4 * NA * yh + (r5 >> 3)) * W + (r5 & 7)) * 32 + 4 * hl;
-    const int ostep = 4 * W * 32;
-    float bv[4][4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) bv[g][i] = bias ? bias[8 * g + 4 * hl + i] : 0.f;
-
-    auto geometry = [&](int t, P32Geo& g) {                  // scalar: tile index -> origin and validity mask (clamped past the end)
-        t = min(t, t_end - 1);
-        const int tx = t % tilesX; t /= tilesX;
-        const int ty = t % tilesY; t /= tilesY;
-        const int tz = t % tilesZ;
-        const int b = t / tilesZ;
-        g.z0 = tz * CL_TZ; g.y0 = ty * CL_TY; g.x0 = tx * CL_TX;
-        g.org = ((((long long)b * D + g.z0) * H + g.y0) * W + g.x0) * 32;
-        g.b = b;
-        // valid halo coordinates h: 0 <= c0 + h - 1 < extent  <=>  h in [max(0, 1 - c0), min(n, extent - c0 + 1))
-        auto bits = [](int c0, int extent, int n) {
-            const int lo = c0 >= 1 ? 0 : 1, hi = min(n, extent - c0 + 1);
-            return ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-        };
-        g.mask = bits(g.z0, D, CL_HZ) | (bits(g.y0, H, CL_HY) << 6) | (bits(g.x0, W, CL_HX) << 16);
-    };
-    // Halo loads are UNCONDITIONAL: a piece outside the volume reads the tile's origin voxel instead (a valid address) and is
-    // zeroed when it is written to LDS, so every wave issues exactly NST loads per tile (counted vmcnt waits)
-    auto load_piece = [&](const P32Geo& g, int it, uint4 (&stg)[NST]) {
-        const bool in = (g.mask & need[it]) == need[it];
-        stg[it] = *reinterpret_cast<const uint4*>(X + g.org + (in ? rel[it] : 0));
-    };
-    auto store_piece = [&](const P32Geo& g, int it, const uint4 (&stg)[NST], unsigned short* img) {
-        const bool in = (g.mask & need[it]) == need[it];
-        uint4 v = stg[it];
-        if (!in) v = make_uint4(0, 0, 0, 0);
-        *reinterpret_cast<uint4*>(img + lofs[it]) = v;
-    };
-
-    float st1[4][4], st2[4][4];                              // this lane's channels 8 g + 4 hl + i, summed over its voxels of the current sample
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) st1[g][i] = st2[g][i] = 0.f;
-    int stat_b = -1;
-    __shared__ float sred[NW * 64];
-    auto flush_stats = [&](int bsample) {                    // uniform call: all threads, between two tiles
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float a = st1[g][i], q2 = st2[g][i];
-#pragma unroll
-                for (int o = 1; o < 32; o <<= 1) { a += __shfl_xor(a, o, 64); q2 += __shfl_xor(q2, o, 64); }
-                if (r5 == 0) { sred[(wave * 32 + 8 * g + 4 * hl + i) * 2] = a; sred[(wave * 32 + 8 * g + 4 * hl + i) * 2 + 1] = q2; }
-                st1[g][i] = st2[g][i] = 0.f;
-            }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            float v = 0.f;
-            for (int w = 0; w < NW; ++w) v += sred[w * 64 + threadIdx.x];
-            stat_part[((long long)bsample * gridDim.x + blockIdx.x) * 64 + threadIdx.x] = v;
-        }
-        __syncthreads();
-    };
-
-    // One tile.  Halo pieces of the two tiles ahead travel in two register sets: set `ld` receives tile n+2 during taps 0..9 (one
-    // piece per tap), set `st` -- requested a whole tile ago -- is written into the other image during taps 10..19.  Each piece
-    // is pinned inside its tap (sched_barrier), so that its address arithmetic, its load issue or LDS write fills the
-    // vector-issue slots the tap's 8 MFMAs leave free: with one wave per SIMD nothing else would.
-    auto one_tile = [&](int cur, const P32Geo& gcur, const P32Geo& gst, const uint4 (&st)[NST], P32Geo& gld, uint4 (&ld)[NST], int buf) {
-        P32_T(t0);
-        const unsigned short* xh = Xh + buf * P32_XH;
-        unsigned short* xo = Xh + (buf ^ 1) * P32_XH;
-        geometry(cur + 2 * t_stride, gld);                   // (past the end: the last tile again -- loaded and written, never used)
-        f32x16 acc[NA];
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][i] = 0.f;
-        constexpr int LA = P32_LA, RING = P32_LA + 1;        // fragments of tap t+LA are requested before the MFMAs of tap t
-        bf16x8 xfr[RING][2][NA], wfr[RING][2];
-        auto fetch = [&](int n) {
-            const int imm = ((n / 9) * CL_HY + (n / 3) % 3) * P32_RP * P32_VS;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-                for (int a = 0; a < NA; ++a)
-                    xfr[n % RING][ks][a] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(xh + abase[n % 3][ks] + imm + a * ASTEP));
-                wfr[n % RING][ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(Bs + bbase + (n * 2 + ks) * 512));
-            }
-        };
-#pragma unroll
-        for (int n = 0; n < LA; ++n) fetch(n);
-#pragma unroll
-        for (int t = 0; t < 27; ++t) {
-            if (t + LA < 27) fetch(t + LA);
-            if (t < NST) load_piece(gld, t, ld);
-            else if (t < 2 * NST) store_piece(gst, t - NST, st, xo);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int a = 0; a < NA; ++a)     // transposed: D[cout][voxel r5] += W[cout][16 channels] . X[16 channels][voxel]
-                    acc[a] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wfr[t % RING][ks], xfr[t % RING][ks][a], acc[a], 0, 0, 0);
-#if P32_SGB      // ask for MFMA / LDS reads / VALU in turn: an in-order wave hides other work only in the issue cycles an MFMA leaves free
-#pragma unroll
-            for (int gq = 0; gq < 2; ++gq) {                 // per tap: 2 NA MFMAs, 2 NA + 2 fragment reads
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2 * P32_SGB, 0);
-            }
-            if (NA == 2) {
-#pragma unroll
-                for (int gq = 0; gq < 2; ++gq) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 2 * P32_SGB, 0);
-                }
-            }
-#endif
-#if P32_PIN
-            if (t < 2 * NST) __builtin_amdgcn_sched_barrier(0);
-#endif
-        }
-        P32_T(t4);
-        {
-            bf16* yb = Y + gcur.org + obase;
-            const bool zok = gcur.z0 + zs < D, xok = gcur.x0 + (r5 & 7) < W;
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                if (zok && xok && gcur.y0 + 4 * (NA * yh + a) + (r5 >> 3) < H) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const unsigned lo = pack_bf16x2(acc[a][4 * g] + bv[g][0], acc[a][4 * g + 1] + bv[g][1]);
-                        const unsigned hi = pack_bf16x2(acc[a][4 * g + 2] + bv[g][2], acc[a][4 * g + 3] + bv[g][3]);
-                        st8_untracked(yb + a * ostep + 8 * g, lo, hi);
-                        if (STATS) {          // (uniform) statistics of the values as stored
-                            const float v0 = __uint_as_float(lo << 16), v1 = __uint_as_float(lo & 0xffff0000u);
-                            const float v2 = __uint_as_float(hi << 16), v3 = __uint_as_float(hi & 0xffff0000u);
-                            st1[g][0] += v0; st2[g][0] += v0 * v0; st1[g][1] += v1; st2[g][1] += v1 * v1;
-                            st1[g][2] += v2; st2[g][2] += v2 * v2; st1[g][3] += v3; st2[g][3] += v3 * v3;
-                        }
-                    }
-                }
-            }
-        }
-        P32_T(t5);
-        __syncthreads();                                     // this tile's image consumed, the next one complete
-        P32_T(t6);
-#ifdef P32_STAMP
-        seg[0] += t4 - t0; seg[3] += t5 - t4; seg[4] += t6 - t5;
-#endif
     };
 
     uint4 sa[NST], sb[NST];
@@ -1706,9 +1341,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32x_kernel(const bf16* __
 #pragma unroll
     for (int it = 0; it < NST; ++it) store_piece(g0, it, sa, Xh);
     __syncthreads();
-#ifdef P32_STAMP
-    P32_T(k1);
-#endif
     for (; tile < t_end; tile += 2 * t_stride) {             // tile j of this workgroup's sequence: image j % 2, store set (j+1) % 2
         if (STATS && g0.b != stat_b) { if (stat_b >= 0) flush_stats(stat_b); stat_b = g0.b; }
         one_tile(tile, g0, g1, sb, g2, sa, 0);               // computes g0, writes g1's halo (sb), requests g2 into sa
@@ -1720,14 +1352,6 @@ __global__ __launch_bounds__(64 * NW, 1) void conv_k3_p32x_kernel(const bf16* __
         // after the swap: g0 = the tile to compute, whose halo is in image 0 -- its data travelled in sa; g1 = requested into sb
     }
     if (STATS && stat_b >= 0) flush_stats(stat_b);
-#ifdef P32_STAMP
-    P32_T(k2);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (int i = 0; i < 6; ++i) p32_stamps[i] = seg[i];
-        p32_stamps[6] = k1 - k0;
-        p32_stamps[7] = k2 - k1;
-    }
-#endif
 }
 
 // First layer (ONE input channel -> 16 * NT): K = 27 taps, padded to a single 32-wide k-step whose A fragment is gathered
@@ -2026,10 +1650,7 @@ constexpr int WG_TZ = 4, WG_TY = 4, WG_TX = 8;                       // voxel ti
 constexpr int WG_HZ = WG_TZ + 2, WG_HY = WG_TY + 2, WG_HX = WG_TX + 2;   // halo tile
 constexpr int WG_NV = WG_TZ * WG_TY * WG_TX;                          // 128 voxels = 4 MFMA k-steps
 constexpr int WG_NH = WG_HZ * WG_HY * WG_HX;                          // 360 halo voxels
-#ifndef WG_PAD
-#define WG_PAD 1     // 0: natural LDS pitches (A/B timing builds)
-#endif
-constexpr int WG_XP = WG_PAD ? 12 : WG_HX;                                             // x pitch of the halo's LDS image (voxels): see wgrad_k3_bf16_kernel
+constexpr int WG_XP = 12;                                             // x pitch of the halo's LDS image (voxels): see wgrad_k3_bf16_kernel
 
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned short* lds_lo, const unsigned short* lds_hi) {
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)lds_lo);
@@ -2055,8 +1676,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void wgrad_k3_bf16_kernel
     //   X halo: 8 dwords per voxel (q -> 0, 8, 16, 24); x pitch padded from 10 to 12 voxels = 96 dwords (kg -> +32)
     //   G tile: voxel stride GVS (NT = 4: 40 dwords, q -> 0, 40, 16, 56; else the natural 8 NT), row stride GRS = 8 GVS + pad = 32
     //           (NT = 2: 8) mod 64 dwords
-    constexpr int GVS = WG_PAD && NT == 4 ? 80 : CB;             // elements
-    constexpr int GRS = 8 * GVS + (!WG_PAD ? 0 : NT == 2 ? 16 : 64);
+    constexpr int GVS = NT == 4 ? 80 : CB;                       // elements
+    constexpr int GRS = 8 * GVS + (NT == 2 ? 16 : 64);
     __shared__ __attribute__((aligned(16))) unsigned short Xh[WG_HZ * WG_HY * WG_XP * 16];
     __shared__ __attribute__((aligned(16))) unsigned short Gt[(WG_NV / 8) * GRS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2206,12 +1827,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void wgrad_k3_bf16_kernel
 // (27 MFMAs per 32 voxels at 1/16 utilisation, two barriers per 128-voxel tile, one tile of prefetch: 91 us for 120 MB).
 // Here the product is laid out the other way round: D[tap (32, 27 used)][co (16)] += Xp^T[tap][voxel] . G[voxel][co], TWO MFMAs per
 // 32 voxels; the A fragment of a tap is 8 x-neighbours of the halo row, read with one ds_read_b128 from one of three copies of
-// the (1.2 KB) halo pre-shifted by dx; persistent workgroups walk 4x8x8 tiles with the gy tiles of the next DEPTH tiles in flight
+// the (1.2 KB) halo pre-shifted by dx; persistent workgroups walk 4x8x8 tiles with the gy tiles of the next WC1_SETS tiles in flight
 // in registers.  A pure stream of gy.
 // ------------------------------------------------------------------------------------------------
-#ifndef WC1_DEPTH
-#define WC1_DEPTH 3
-#endif
+constexpr int WC1_SETS = 3;                                 // gy tiles in flight per workgroup (register sets)
 // NB ("norm backward on load"): GY is the gradient w.r.t. the OUTPUT of the normalisation that follows the first convolution, Z that
 // normalisation's input; the data gradient gz of the normalisation -- whose only consumer is this weight gradient, the first
 // convolution has no data gradient -- is formed per element while the tile is written to LDS (nb[] = per (sample, channel)
@@ -2374,19 +1993,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_k3_c1_kernel(const bf16* __restr
     };
 
     if (tile < t_end) {
-        Stage st[WC1_DEPTH];
-        Geo gg[WC1_DEPTH];
+        Stage st[WC1_SETS];
+        Geo gg[WC1_SETS];
 #pragma unroll
-        for (int d = 0; d < WC1_DEPTH; ++d) { geometry(tile + d * t_stride, gg[d]); load_tile(gg[d], st[d]); }
-        // tile j of this workgroup travels in set j % DEPTH; the loop is unrolled DEPTH times so that the sets are compile-time
-        for (; tile < t_end; tile += WC1_DEPTH * t_stride) {
+        for (int d = 0; d < WC1_SETS; ++d) { geometry(tile + d * t_stride, gg[d]); load_tile(gg[d], st[d]); }
+        // tile j of this workgroup travels in set j % WC1_SETS; the loop is unrolled WC1_SETS times so that the sets are compile-time
+        for (; tile < t_end; tile += WC1_SETS * t_stride) {
 #pragma unroll
-            for (int d = 0; d < WC1_DEPTH; ++d) {
+            for (int d = 0; d < WC1_SETS; ++d) {
                 if (tile + d * t_stride < t_end) {              // (uniform)
                     __syncthreads();                            // previous tile consumed
                     store_tile(gg[d], st[d]);
-                    geometry(tile + (d + WC1_DEPTH) * t_stride, gg[d]);
-                    load_tile(gg[d], st[d]);                    // DEPTH tiles ahead (clamped past the end: loaded, never stored)
+                    geometry(tile + (d + WC1_SETS) * t_stride, gg[d]);
+                    load_tile(gg[d], st[d]);                    // WC1_SETS tiles ahead (clamped past the end: loaded, never stored)
                     __syncthreads();
                     compute();
                 }
@@ -2627,21 +2246,21 @@ __global__ __launch_bounds__(256, 2) void first_block_bwd_kernel(const bf16* __r
         sg = sgz = sz = 0.f;
     };
 
-    Stage st[WC1_DEPTH];
-    Geo gg[WC1_DEPTH];
+    Stage st[WC1_SETS];
+    Geo gg[WC1_SETS];
     int acc_b = -1;
 #pragma unroll
-    for (int d = 0; d < WC1_DEPTH; ++d) { geometry(tile + d * t_stride, gg[d]); load_tile(gg[d], st[d]); }
-    for (; tile < t_end; tile += WC1_DEPTH * t_stride) {
+    for (int d = 0; d < WC1_SETS; ++d) { geometry(tile + d * t_stride, gg[d]); load_tile(gg[d], st[d]); }
+    for (; tile < t_end; tile += WC1_SETS * t_stride) {
 #pragma unroll
-        for (int d = 0; d < WC1_DEPTH; ++d) {
+        for (int d = 0; d < WC1_SETS; ++d) {
             if (tile + d * t_stride < t_end) {                  // (uniform)
                 const unsigned cur_mask = gg[d].mask;
                 const int cur_b = gg[d].b;
                 if (cur_b != acc_b) { if (acc_b >= 0) flush(acc_b); acc_b = cur_b; }
                 __syncthreads();
                 store_tile(gg[d], st[d]);
-                geometry(tile + (d + WC1_DEPTH) * t_stride, gg[d]);
+                geometry(tile + (d + WC1_SETS) * t_stride, gg[d]);
                 load_tile(gg[d], st[d]);
                 __syncthreads();
                 compute(cur_mask);
@@ -2732,9 +2351,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_k2s2_bf16_kernel(const bf16* __r
     // bank-conflict-free LDS images for the transposed reads, as in wgrad_k3_bf16_kernel.  HI: a lane group reads voxels 2q (+dx) of
     // the HI rows 2 kg (+dy) -- 16 q dwords apart, so the rows of kg and kg + 1 must land 8 (mod 16) dwords apart: x-row pitch
     // 16 voxels + 16 bytes (two rows = 264 dwords = 8 mod 64)
-    constexpr int HXP = HX * 16 + (WG_PAD ? 8 : 0);                     // elements
-    constexpr int GVS = WG_PAD && NT == 4 ? 80 : CB;
-    constexpr int GRS = 8 * GVS + (!WG_PAD ? 0 : NT == 2 ? 16 : 64);
+    constexpr int HXP = HX * 16 + 8;                                    // elements
+    constexpr int GVS = NT == 4 ? 80 : CB;
+    constexpr int GRS = 8 * GVS + (NT == 2 ? 16 : 64);
     __shared__ __attribute__((aligned(16))) unsigned short Xh[HZ * HY * HXP];
     __shared__ __attribute__((aligned(16))) unsigned short Gt[(WG_NV / 8) * GRS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3274,13 +2893,8 @@ static SplitK splitk_plan(int dtype, int mode, int scatter, long long M, int N, 
 static bool conv_tile_ok(int dtype, int mode, int scatter, long long DHW, int Cin, int N) {
     return dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && Cin % 32 == 0 && N % CT_BN == 0 && Cin >= 64 && DHW < 13824;
 }
-// tunables read once from the environment (diagnostic sweeps only; the defaults are what ships)
-static long long env_ll(const char* name, long long dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoll(v) : dflt;
-}
 static SplitK conv_tile_plan(long long M, int N, int Cin) {
-    static const long long target_wgs = env_ll("DYCON_TILE_SPLIT_WGS", 512);
+    constexpr long long target_wgs = 512;
     const int nKC = 27 * Cin / 32;
     const long long wgs = ((M + CT_BM - 1) / CT_BM) * (N / CT_BN);
     SplitK p{1, nKC};
@@ -3367,9 +2981,8 @@ extern "C" int dycon_conv_gemm(const void* x, const void* wfrag, const float* bi
 static thread_local float* g_stat_part = nullptr;      // set by dycon_conv_gemm_stats around its call of dycon_conv_gemm_ex
 
 static bool conv_p32_shape(int dtype, int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
-    static const bool p32_on = env_ll("DYCON_P32", 1) != 0;
     const int nTiles = B * cdiv(Di, CL_TZ) * cdiv(Hi, CL_TY) * cdiv(Wi, CL_TX);
-    return p32_on && dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && !accumulate && Cin == 32 && Cout == 32 &&
+    return dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && !accumulate && Cin == 32 && Cout == 32 &&
            (long long)Di * Hi * Wi >= 13824 && nTiles >= 1024;
 }
 // rows per sample of the statistics partials a dycon_conv_gemm_stats call of this shape writes (0: shape not served)
@@ -3439,23 +3052,11 @@ extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float*
             return DYCON_OK;
         }
         // 32 -> 32 with several tiles per CU: persistent kernel, weights stationary in LDS (one workgroup per CU)
-        static const bool p32_on = env_ll("DYCON_P32", 1) != 0;
-        if (p32_on && Cin == 32 && Cout == 32 && !accumulate && nTiles >= 1024) {
+        // (a 32x32x16 MFMA form measured slower, 30.9 against 28.5 us per launch at 48^3, and was removed: DESIGN section 9)
+        if (Cin == 32 && Cout == 32 && !accumulate && nTiles >= 1024) {
             const int per_xcd = min(cdiv(nTiles, 8), 32);
-            static const long long p32_nw = env_ll("DYCON_P32_WAVES", 8);
-            // DYCON_P32X=1: the 32x32x16 MFMA form (conv_k3_p32x_kernel).  Measured SLOWER (30.9 vs 28.5 us per launch at 48^3, step
-            // unchanged): equal MFMA cycles per tap, and the chip holds a lower clock on the 32x32 shape (MI355X_MICROARCH.md, DVFS
-            // give-back item 7) -- what the freed issue slots return does not make up for it.  Kept (tested), off.  Read per call:
-            // the tests switch it inside one process.
-            const bool p32x = env_ll("DYCON_P32X", 0) != 0;
-#define DYCON_P32(KRN, NWV, STV) KRN<NWV, STV><<<8 * per_xcd, 64 * NWV, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, tz, ty, tx, nTiles, g_stat_part)
-            if (p32x) {
-                if (p32_nw == 8) { if (g_stat_part) DYCON_P32(conv_k3_p32x_kernel, 8, true); else DYCON_P32(conv_k3_p32x_kernel, 8, false); }
-                else { if (g_stat_part) DYCON_P32(conv_k3_p32x_kernel, 4, true); else DYCON_P32(conv_k3_p32x_kernel, 4, false); }
-            } else {
-                if (p32_nw == 8) { if (g_stat_part) DYCON_P32(conv_k3_p32_kernel, 8, true); else DYCON_P32(conv_k3_p32_kernel, 8, false); }
-                else { if (g_stat_part) DYCON_P32(conv_k3_p32_kernel, 4, true); else DYCON_P32(conv_k3_p32_kernel, 4, false); }
-            }
+#define DYCON_P32(STV) conv_k3_p32_kernel<8, STV><<<8 * per_xcd, 64 * 8, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, tz, ty, tx, nTiles, g_stat_part)
+            if (g_stat_part) DYCON_P32(true); else DYCON_P32(false);
 #undef DYCON_P32
             DYCON_LAUNCH_CHECK();
             return DYCON_OK;
@@ -3466,9 +3067,8 @@ extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float*
         if (Cin == 16 || Cin == 48) {
             if (ntb == 1) DYCON_CL(16, 1, 4); else if (ntb == 2) DYCON_CL(16, 2, 4); else if (ntb == 3) DYCON_CL(16, 3, 4); else DYCON_CL(16, 4, 2);
         } else {
-            static const bool w8_on = env_ll("DYCON_LDS_W8", 1) != 0;
             if (ntb == 1) DYCON_CL(32, 1, 4); else if (ntb == 2) DYCON_CL(32, 2, 4); else if (ntb == 3) DYCON_CL(32, 3, 4);
-            else if (w8_on && (long long)nTiles * (NT / ntb) <= 256)     // at most one workgroup per CU: 8 waves, two per SIMD (a wave per SIMD is issue-bound)
+            else if ((long long)nTiles * (NT / ntb) <= 256)     // at most one workgroup per CU: 8 waves, two per SIMD (a wave per SIMD is issue-bound)
                 conv_k3_lds_kernel<32, 4, 4, 8><<<grid, 512, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, Cin, Cout, NT, tz, ty, tx, accumulate);
             else DYCON_CL(32, 4, 2);
         }
@@ -3493,10 +3093,8 @@ extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float*
         SplitK sk = conv_tile_plan(M, N, Cin);
         const bool split = sk.splits > 1 && workspace && ws_bytes >= (size_t)sk.splits * M * N * sizeof(float);
         dim3 grid(cdiv(M, CT_BM), N / CT_BN, split ? sk.splits : 1);
-        static const bool tile64 = env_ll("DYCON_TILE_KS64", 1) != 0;
-        static const bool lds_epi = env_ll("DYCON_TILE_LDS_EPI", 1) != 0;
-        const int layout = split && defer_finish ? 1 : lds_epi ? 0 : 2;
-        if (tile64 && Cin % 64 == 0 && sk.kc_per_split % 2 == 0)
+        const int layout = split && defer_finish ? 1 : 0;
+        if (Cin % 64 == 0 && sk.kc_per_split % 2 == 0)
             conv_k3_tile_kernel<2><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, split ? workspace : nullptr, B,
                                                              Di, Hi, Wi, Cin, N, NT, nKC, sk.kc_per_split, accumulate, layout);
         else
@@ -3615,7 +3213,7 @@ static WgradK3Plan wgrad_k3_plan(int B, int D, int H, int W, int Cin, int Cout) 
     p.gx = ((Cin + 15) / 16) * p.nCoBlk;
     const long long L = 27LL * Cin * Cout;
     long long s = 2048 / p.gx;
-    static const long long slab_mb = env_ll("DYCON_WGRAD_SLAB_MB", 24);
+    constexpr long long slab_mb = 24;
     const long long cap = (slab_mb << 20) / (4 * L) > 0 ? (slab_mb << 20) / (4 * L) : 1;   // partial slabs capped at ~24 MB (fewer splits = fewer workgroups = slower: measured)
     if (s > cap) s = cap;
     if (s > p.nTiles) s = p.nTiles;
@@ -3780,8 +3378,7 @@ extern "C" int dycon_conv_wgrad(const void* x, int x_dtype, const void* gy, int 
     const WgradPlan p = wgrad_plan(mode, B, Di, Hi, Wi, Cin, Cout);
     if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16 && wgrad_k3_ok(mode, Cin, Cout)) {
         const WgradK3Plan k = wgrad_k3_plan(B, Di, Hi, Wi, Cin, Cout);
-        static const bool wc1_on = env_ll("DYCON_WGRAD_C1", 1) != 0;
-        if (wc1_on && Cin == 1 && Cout == 16) {      // first layer: transposed product, persistent workgroups (wgrad_k3_c1_kernel)
+        if (Cin == 1 && Cout == 16) {      // first layer: transposed product, persistent workgroups (wgrad_k3_c1_kernel)
             const int tz = cdiv(Di, CL_TZ), ty = cdiv(Hi, CL_TY), tx = cdiv(Wi, CL_TX);
             const int nTiles = B * tz * ty * tx;
             const int wgs = wgrad_c1_wgs(B, Di, Hi, Wi);
@@ -3796,8 +3393,7 @@ extern "C" int dycon_conv_wgrad(const void* x, int x_dtype, const void* gy, int 
         dim3 grid(k.gx, k.splits);
 #define DYCON_WK3(NTV, C1) \
     wgrad_k3_bf16_kernel<NTV, C1><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX)
-        static const bool wg_w8 = env_ll("DYCON_WGRAD_W8", 1) != 0;
-        if (wg_w8 && Cin != 1 && k.NT == 4 && (long long)k.gx * k.splits <= 256)      // at most one workgroup per CU: 8 waves, two per SIMD
+        if (Cin != 1 && k.NT == 4 && (long long)k.gx * k.splits <= 256)      // at most one workgroup per CU: 8 waves, two per SIMD
             wgrad_k3_bf16_kernel<4, false, 8><<<grid, 512, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX);
         else if (Cin == 1) { if (k.NT == 1) DYCON_WK3(1, true); else if (k.NT == 2) DYCON_WK3(2, true); else DYCON_WK3(4, true); }
         else if (k.NT == 1) DYCON_WK3(1, false);

@@ -261,9 +261,6 @@ __global__ __launch_bounds__(256) void mask_pool_kernel(const void* __restrict__
 //   different-class pairs with f_i.t_j > thr, summed over the batch / their count.
 // =================================================================================================
 constexpr int FT = 64;  // tile edge
-#ifndef FECL_P4_PREF
-#define FECL_P4_PREF 0
-#endif
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
@@ -515,12 +512,12 @@ __global__ __launch_bounds__(256) void fecl_kernel(const T* __restrict__ F, cons
     // that retires it -- the global round trip no longer sits between two barriers with nothing else to do.
     constexpr int NPF = 8;                                // 64 rows x 256 bf16 = 2048 pieces / 256 threads
     // (not in the gradient pass: its 64 accumulator registers plus a staged tile leave room for one wave per SIMD only -- measured slower)
-    const bool pref = (PASS != 4 || FECL_P4_PREF) && sizeof(T) == 2 && (Dm & 7) == 0 && Dp <= 256;
+    const bool pref = PASS != 4 && sizeof(T) == 2 && (Dm & 7) == 0 && Dp <= 256;
     uint4 pfr[NPF];
     // A thread's piece of a staged tile: with 256 % (pieces per row) == 0 (Dp = 32 .. 256 in powers of two) its column never changes
     // and its row advances by a fixed step, so nothing is divided per piece -- the e / ppr form below cost ~25 vector instructions per
     // piece, 16 pieces per tile: 400 of the 468 VALU instructions per tile and wave that PMC counted in pass 1
-    // (profiles/r03_fecl_pmc.txt), with the vector ALU the busiest pipe of passes 1 and 2.
+    // (profiles/r03_fecl_n15680.txt), with the vector ALU the busiest pipe of passes 1 and 2.
     const int ppr_ = Dp >> 3;
     const bool lin = 256 % ppr_ == 0;
     const int rstep = lin ? 256 / ppr_ : 0, rr0 = threadIdx.x / ppr_, k0 = (threadIdx.x - rr0 * ppr_) << 3;
@@ -1326,8 +1323,7 @@ static int fecl_launch(const void* feat, const void* teacher, const float* mask,
 // reference runs (gamma = 2) or none, and N >= 1024 (8 row blocks per sample; the headline N = 1728 runs 0.27 -> 0.25 ms alone
 // and the step 4.72 -> 4.64 ms with them, profiles/r03_fecl_n15680.txt)
 static bool fecl_rows128_ok(int dtype, int B, int N, int Dm, float gamma, int focal) {
-    static const long long min_n = [] { const char* v = getenv("DYCON_FECL_ROWS128_MIN_N"); return v && *v ? atoll(v) : 1024LL; }();
-    return dtype == DYCON_BF16 && (Dm == 64 || Dm == 128 || Dm == 256) && (!focal || gamma == 2.f) && N >= min_n;
+    return dtype == DYCON_BF16 && (Dm == 64 || Dm == 128 || Dm == 256) && (!focal || gamma == 2.f) && N >= 1024;
 }
 template <int PASS, int NQ>
 static int fecl_rows128_launch_nq(const void* feat, const void* teacher, const float* mask, const float* gamb, int B, int N, int Dm,

@@ -14,9 +14,8 @@
 struct NormPlan { int chunks; long long rows_per_chunk; };
 static NormPlan norm_plan(long long V) {
     NormPlan p;
-    static const long long maxc = [] { const char* v = getenv("DYCON_NORM_CHUNKS"); return v && *v ? atoll(v) : 256LL; }();
+    constexpr long long maxc = 256, minr = 128;
     long long rpc = (V + maxc - 1) / maxc;     // <= 256 chunks per sample ...
-    static const long long minr = [] { const char* v = getenv("DYCON_NORM_MIN_ROWS"); return v && *v ? atoll(v) : 128LL; }();
     if (rpc < minr) rpc = minr;          // ... of >= 128 rows.  (Round 3: 512 chunks of >= 64 rows -> 256 of >= 128: the step 4.54 -> 4.47 ms over two
                                          // pairs, profiles/r03_norm_chunk_plan.txt -- per-workgroup fixed cost (launch ramp, the LDS tree, the partial
                                          // stores and the finalize that sums them) against the length of the serial row loop; 128 / 1024 chunks are slower.)
@@ -733,8 +732,7 @@ extern "C" int dycon_norm_fwd(const void* x, void* y, int dtype, int Nb, long lo
 }
 
 static int apply_grid(long long V, int C, int VN) {
-    static const long long vpt = [] { const char* v = getenv("DYCON_NORM_APPLY_VPT"); return v && *v ? atoll(v) : 4LL; }();
-    static const long long cap = [] { const char* v = getenv("DYCON_NORM_APPLY_CAP"); return v && *v ? atoll(v) : 2048LL; }();
+    constexpr long long vpt = 4, cap = 2048;                  // vectors per thread, workgroups per sample
     long long blocks = (V * C / VN + 256 * vpt - 1) / (256 * vpt);
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;

@@ -247,10 +247,10 @@ def test_step_full_size_vs_oracle(name, patch, okw, tkw):
 
 
 @pytest.mark.parametrize("sp", [(48, 48, 48), (46, 50, 44)])
-def test_conv_p32_on_32x32x16_mfma(sp, monkeypatch):
-    """conv_k3_p32x_kernel (DYCON_P32X=1: the persistent 48^3 kernel on v_mfma_f32_32x32x16_bf16 -- measured slower, off by default)
-    against F.conv3d element-wise, against the default kernel within one bf16 step (the k order inside a tap differs), and its
-    statistics epilogue against the default kernel's."""
+def test_conv_p32_persistent(sp):
+    """conv_k3_p32_kernel (the persistent 48^3 kernel, 32 -> 32 channels) against F.conv3d element-wise; its statistics form stores
+    the same output bit for bit, and its partials add up to the per-(sample, channel) {sum, sum of squares} of the stored output.
+    Ragged shape: partial tiles must neither store nor count their padding."""
     from dycon_paper_replication_amd._lib import CONV_K3
     rng = np.random.default_rng(sp[1])
     B, C = 4, 32
@@ -259,20 +259,19 @@ def test_conv_p32_on_32x32x16_mfma(sp, monkeypatch):
     b = torch.from_numpy(rng.standard_normal(C).astype(np.float32))
     wf = ops.pack_bfrag(w.to(DEV), BF, 27, C, C, C, 1, 27, 0, C * 27)
     chunks = ops.conv_stats_chunks(x, C, C)
-    res = {}
-    for v in ("0", "1"):
-        monkeypatch.setenv("DYCON_P32X", v)
-        y = ops.conv_gemm(x, wf, b.to(DEV), CONV_K3, C, C)
-        y2, part = ops.conv_gemm_stats(x, wf, b.to(DEV), C, chunks)
-        torch.cuda.synchronize()
-        assert torch.equal(y, y2)
-        res[v] = (y, part.reshape(B, chunks, C, 2).sum(1))
+    assert chunks > 0
+    y = ops.conv_gemm(x, wf, b.to(DEV), CONV_K3, C, C)
+    y2, part = ops.conv_gemm_stats(x, wf, b.to(DEV), C, chunks)
+    torch.cuda.synchronize()
+    assert torch.equal(y, y2)
     ref = F.conv3d(x.float().cpu().permute(0, 4, 1, 2, 3), w.bfloat16().float(), b, padding=1)
-    assert_bf16_elementwise(nc(res["1"][0]), ref, f"p32x y @ {sp}")
-    assert_bf16_elementwise(nc(res["0"][0]), ref, f"p32 y @ {sp}")
-    d = (res["1"][0].float() - res["0"][0].float()).abs()
-    assert float((d > 2.0 ** -7 * res["0"][0].float().abs() + 1e-3).float().mean()) == 0.0
-    np.testing.assert_allclose(res["1"][1].cpu().numpy(), res["0"][1].cpu().numpy(), rtol=2e-3, atol=0.5)
+    assert_bf16_elementwise(nc(y), ref, f"p32 y @ {sp}")
+    got = part.double().reshape(B, chunks, C, 2).sum(1).cpu()
+    yd = y.double().cpu()
+    s1, s2, a1 = yd.sum((1, 2, 3)), (yd * yd).sum((1, 2, 3)), yd.abs().sum((1, 2, 3))
+    # fp32 summation order only: the partials and the host sums add up the same stored bf16 values
+    assert float(((got[..., 0] - s1).abs() - 1e-5 * a1).max()) <= 0, f"sum @ {sp}"
+    np.testing.assert_allclose(got[..., 1].numpy(), s2.numpy(), rtol=1e-5, atol=0)
 
 
 @pytest.mark.parametrize("cin,C,sp", [(32, 32, (48, 48, 48)), (32, 32, (46, 50, 44)), (16, 16, (96, 96, 96)), (16, 16, (50, 44, 46)),
