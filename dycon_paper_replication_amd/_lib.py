@@ -94,6 +94,14 @@ SIGNATURES = {
     "dycon_fecl_finalize": (I, [P, C.c_double, F, I, P, P]),
     "dycon_set_scalars": (I, [P, I, F, F, F, F, F, F, F, F, P]),
     "dycon_fecl_bwd": (I, [P, P, P, P, I, I, I, I, F, F, I, F, F, P, P, P, P, Z, P]),
+    "dycon_fecl_rows_workspace": (Z, [I, I, I]),
+    "dycon_fecl_fwd_rows": (I, [P, P, P, P, I, I, I, I, F, F, P, P, Z, Z, P]),
+    "dycon_fecl_gambling_finalize": (I, [P, P, I, I, I, I, P, P, P, P, Z, P, Z, P]),
+    "dycon_fecl_gambling_grad": (I, [P, P, L, P, P]),
+    "dycon_gambling_softmax_fwd": (I, [P, P, L, I, P]),
+    "dycon_gambling_softmax_bwd": (I, [P, P, P, L, I, P]),
+    "dycon_gambling_uncertainty_fwd": (I, [P, I, I, I, I, I, I, I, P, I, P]),
+    "dycon_gambling_uncertainty_bwd": (I, [P, I, I, I, I, I, I, I, P, P, I, P]),
     "dycon_sumsq": (I, [P, L, P, P]),
     "dycon_sgd_ema": (I, [P, P, P, P, L, L, P, F, F, F, F, F, F, P, P]),
     "dycon_nonfinite_flag": (I, [P, P, P]),

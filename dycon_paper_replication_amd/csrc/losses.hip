@@ -432,13 +432,16 @@ __device__ __forceinline__ void fast_pair(float lm /* L - m */, float n, float& 
     adphi = n * r * (2.f * a * lgP - n);
 }
 
-// PASS: 1 row max | 2 negative sums + class counts | 3 loss + H (+ cross sums) | 4 gradient
-template <typename T, int PASS>
+// PASS: 1 row max | 2 negative sums + class counts | 3 loss + H (+ cross sums) | 4 gradient.  ROWS (pass 3 of dycon_fecl_fwd_rows only):
+// also store the row sums to rsl; a compile-time switch, so every other instantiation is the kernel without the store
+template <typename T, int PASS, bool ROWS = false>
 __global__ __launch_bounds__(256) void fecl_kernel(const T* __restrict__ F, const T* __restrict__ Tch,
                                                    const float* __restrict__ mask, const float* __restrict__ gamb, int N, int Dm,
                                                    float tau, float gamma, int focal, float thr, float* __restrict__ ws,
                                                    double* __restrict__ out, const float* __restrict__ coef, float lambda_cross,
-                                                   float* __restrict__ GS, int Btot, int CS, int tiles_per_split) {
+                                                   float* __restrict__ GS, int Btot, int CS, int tiles_per_split,
+                                                   float* __restrict__ rsl) {
+    // rsl (ROWS only): [CS][BN] partial sums of the row's same-class pair terms, sum_j ell_ij (dycon_fecl_fwd_rows)
     // blockIdx.z = column split: this workgroup walks column tiles [z*tiles_per_split, (z+1)*tiles_per_split) and writes
     // its PARTIAL row results into slab z; consumers combine the CS slabs on load (max / ordered sum): deterministic.
     typedef typename FeclTile<T>::E E;
@@ -746,6 +749,7 @@ __global__ __launch_bounds__(256) void fecl_kernel(const T* __restrict__ F, cons
                 const float u = gamb ? gamb[rb + gi[i]] : 1.f;
                 const float kap = u / (ld_sum(wc, rb + gi[i]) - 1.f + 1e-18f);   // total same-class count from pass 2
                 if (cs == 0) wk[rb + gi[i]] = kap;
+                if (ROWS) rsl[cs * BN + rb + gi[i]] = ph;
                 wh[cs * BN + rb + gi[i]] = kap * hs;
                 lsum += ph * kap;
             }
@@ -793,11 +797,13 @@ constexpr int F2_ROWS = 128;   // rows per workgroup (4 waves x 32)
 constexpr int F2_PAD = 8;      // column-tile row stride Dm + 8 elements = odd number of 16-byte slots: the 32 rows of an A-fragment read
                                // (lanes 0-31 slot 2q, lanes 32-63 slot 2q + 1) fall in 16 distinct slots per ds_read_b128 lane group
 
-template <int PASS, int NQ>     // NQ = Dm / 16 k-steps (compile time: a predicated k-loop made the compiler copy the 32 accumulators per step)
+// NQ = Dm / 16 k-steps (compile time: a predicated k-loop made the compiler copy the 32 accumulators per step); ROWS: as fecl_kernel
+template <int PASS, int NQ, bool ROWS = false>
 __global__ __launch_bounds__(256, 2) void fecl_rows128_kernel(const bf16* __restrict__ F, const bf16* __restrict__ Tch,
                                                               const float* __restrict__ mask, const float* __restrict__ gamb, int N,
                                                               int Dm, float tau, int focal, float thr, float* __restrict__ ws,
-                                                              double* __restrict__ out, int Btot, int CS, int tiles_per_split) {
+                                                              double* __restrict__ out, int Btot, int CS, int tiles_per_split,
+                                                              float* __restrict__ rsl) {   // rsl: as fecl_kernel
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int stride = Dm + F2_PAD, tile_elems = FT * stride;
     unsigned short* Fj = reinterpret_cast<unsigned short*>(lds_raw);                       // [2][64][stride]
@@ -943,6 +949,7 @@ __global__ __launch_bounds__(256, 2) void fecl_rows128_kernel(const bf16* __rest
             const float u = gamb ? gamb[rb + gi] : 1.f;
             const float kap = u / (ld_sum(wc, rb + gi) - 1.f + 1e-18f);   // total same-class count from pass 2
             if (cs == 0) wk[rb + gi] = kap;
+            if (ROWS) rsl[cs * BN + rb + gi] = ph;
             wh[cs * BN + rb + gi] = kap * hs;
             lsum = ph * kap;
         }
@@ -1302,10 +1309,12 @@ template <typename T> static size_t fecl_lds_bytes(int Dm, bool grad) {
 template <typename T, int PASS>
 static int fecl_launch(const void* feat, const void* teacher, const float* mask, const float* gamb, int B, int N, int Dm,
                        float tau, float gamma, int focal, float thr, float* ws, double* out, const float* coef, float lambda_cross,
-                       dycon_stream_t stream) {
+                       dycon_stream_t stream, float* rsl = nullptr) {
     const size_t lds = fecl_lds_bytes<T>(Dm, PASS == 4);
     // > 64 KiB of dynamic LDS needs the opt-in attribute (idempotent, no sync, capture-safe)
-    if (hipFuncSetAttribute((const void*)fecl_kernel<T, PASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    const void* fn = (const void*)fecl_kernel<T, PASS>;
+    if constexpr (PASS == 3) if (rsl) fn = (const void*)fecl_kernel<T, 3, true>;   // (the row-term store exists in pass 3 only)
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         dycon_set_error("fecl: cannot reserve %zu bytes of LDS", lds);
         return DYCON_ERR_LAUNCH;
     }
@@ -1313,8 +1322,16 @@ static int fecl_launch(const void* feat, const void* teacher, const float* mask,
     fecl_split(B, N, false, CS, tps);
     float* gslab = ws + (size_t)(4 * CS + 1) * B * N;
     dim3 grid(cdiv(N, FT), B, CS);
+    if constexpr (PASS == 3) {
+        if (rsl) {
+            fecl_kernel<T, 3, true><<<grid, 256, lds, stream>>>((const T*)feat, (const T*)teacher, mask, gamb, N, Dm, tau, gamma, focal, thr,
+                                                               ws, out, coef, lambda_cross, gslab, B, CS, tps, rsl);
+            DYCON_LAUNCH_CHECK();
+            return DYCON_OK;
+        }
+    }
     fecl_kernel<T, PASS><<<grid, 256, lds, stream>>>((const T*)feat, (const T*)teacher, mask, gamb, N, Dm, tau, gamma, focal, thr, ws,
-                                                    out, coef, lambda_cross, gslab, B, CS, tps);
+                                                    out, coef, lambda_cross, gslab, B, CS, tps, nullptr);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }
@@ -1327,26 +1344,36 @@ static bool fecl_rows128_ok(int dtype, int B, int N, int Dm, float gamma, int fo
 }
 template <int PASS, int NQ>
 static int fecl_rows128_launch_nq(const void* feat, const void* teacher, const float* mask, const float* gamb, int B, int N, int Dm,
-                                  float tau, int focal, float thr, float* ws, double* out, dycon_stream_t stream) {
+                                  float tau, int focal, float thr, float* ws, double* out, dycon_stream_t stream, float* rsl) {
     const size_t lds = ((size_t)2 * FT * (Dm + F2_PAD) * 2 + 15) / 16 * 16 + 2 * 2 * FT * sizeof(float);
-    if (hipFuncSetAttribute((const void*)fecl_rows128_kernel<PASS, NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    const void* fn = (const void*)fecl_rows128_kernel<PASS, NQ>;
+    if constexpr (PASS == 3) if (rsl) fn = (const void*)fecl_rows128_kernel<3, NQ, true>;
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
         dycon_set_error("fecl: cannot reserve %zu bytes of LDS", lds);
         return DYCON_ERR_LAUNCH;
     }
     int CS, tps;
     fecl_split(B, N, true, CS, tps);
     dim3 grid(cdiv(N, F2_ROWS), B, CS);
+    if constexpr (PASS == 3) {
+        if (rsl) {
+            fecl_rows128_kernel<3, NQ, true><<<grid, 256, lds, stream>>>((const bf16*)feat, (const bf16*)teacher, mask, gamb, N, Dm, tau, focal,
+                                                                          thr, ws, out, B, CS, tps, rsl);
+            DYCON_LAUNCH_CHECK();
+            return DYCON_OK;
+        }
+    }
     fecl_rows128_kernel<PASS, NQ><<<grid, 256, lds, stream>>>((const bf16*)feat, (const bf16*)teacher, mask, gamb, N, Dm, tau, focal, thr, ws,
-                                                              out, B, CS, tps);
+                                                              out, B, CS, tps, nullptr);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }
 template <int PASS>
 static int fecl_rows128_launch(const void* feat, const void* teacher, const float* mask, const float* gamb, int B, int N, int Dm,
-                               float tau, int focal, float thr, float* ws, double* out, dycon_stream_t stream) {
-    if (Dm == 256) return fecl_rows128_launch_nq<PASS, 16>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream);
-    if (Dm == 128) return fecl_rows128_launch_nq<PASS, 8>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream);
-    return fecl_rows128_launch_nq<PASS, 4>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream);
+                               float tau, int focal, float thr, float* ws, double* out, dycon_stream_t stream, float* rsl = nullptr) {
+    if (Dm == 256) return fecl_rows128_launch_nq<PASS, 16>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream, rsl);
+    if (Dm == 128) return fecl_rows128_launch_nq<PASS, 8>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream, rsl);
+    return fecl_rows128_launch_nq<PASS, 4>(feat, teacher, mask, gamb, B, N, Dm, tau, focal, thr, ws, out, stream, rsl);
 }
 
 template <int NQ>
@@ -1437,6 +1464,275 @@ extern "C" int dycon_fecl_bwd(const void* feat, const void* teacher, const float
         }
     });
     if (e) return e;
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+// =================================================================================================
+// Gambling-softmax uncertainty (utils/dycon_losses.py:14-26, :209-211; train_DyCON_Pancreas.py:242-246)
+//   p = exp(l) / (sum_c exp(l_c) + 1e-18)            -- no max shift: a logit above ~88.7 gives inf / inf = NaN, as in the reference
+//   H = -sum_c p_c log(p_c + 1e-6);  u = F.interpolate(H, scale_factor = 1/k, trilinear, align_corners = False)
+// With an even k per axis the source coordinate of output i is k i + k/2 - 0.5: u[b, n] is the plain mean of H over the 2 x 2 x 2
+// voxels {k i + k/2 - 1, k i + k/2} per axis, and no voxel belongs to two patches (the adjoint needs no atomics).
+// The FeCL branch then weights the unfocused per-row student term r_i = sum_j ell_ij / (cnt_i - 1 + 1e-18) by u_i.
+// =================================================================================================
+// one voxel: y_c = exp(x_c) / (sum_k exp(x_k) + 1e-18)
+template <int C> __device__ __forceinline__ void gs_fwd_voxel(const float* x, float* y) {
+    float e[C], s = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { e[c] = expf(x[c]); s += e[c]; }
+    const float den = s + 1e-18f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) y[c] = e[c] / den;
+}
+// one voxel: dl_j = p_j (g_j - sum_c g_c p_c)   (p_c = e_c / (S + 1e-18): d p_c / d l_j = delta_cj p_c - p_c p_j)
+template <int C> __device__ __forceinline__ void gs_bwd_voxel(const float* p, const float* g, float* gx) {
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) s += g[c] * p[c];
+#pragma unroll
+    for (int c = 0; c < C; ++c) gx[c] = p[c] * (g[c] - s);
+}
+
+// A thread owns 4 consecutive voxels = C 16-byte pieces of every operand (coalesced dwordx4 loads / stores for any C); the
+// nvox % 4 trailing voxels go to the first threads of workgroup 0.  VEC = 0: the same per voxel with scalar accesses, for operands
+// that are not 16-byte aligned.
+template <int C, bool BWD, bool VEC>
+__global__ __launch_bounds__(256) void gambling_softmax_kernel(const float* __restrict__ a, const float* __restrict__ g,
+                                                               float* __restrict__ out, long long nvox) {
+    const long long nq = VEC ? nvox / 4 : 0;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long long)gridDim.x * blockDim.x) {
+        float va[4 * C], vg[BWD ? 4 * C : 1], vo[4 * C];
+#pragma unroll
+        for (int i = 0; i < C; ++i) {
+            const float4 t = reinterpret_cast<const float4*>(a)[q * C + i];
+            va[4 * i] = t.x; va[4 * i + 1] = t.y; va[4 * i + 2] = t.z; va[4 * i + 3] = t.w;
+            if (BWD) {
+                const float4 h = reinterpret_cast<const float4*>(g)[q * C + i];
+                vg[4 * i] = h.x; vg[4 * i + 1] = h.y; vg[4 * i + 2] = h.z; vg[4 * i + 3] = h.w;
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            if (BWD) gs_bwd_voxel<C>(va + v * C, vg + v * C, vo + v * C);
+            else gs_fwd_voxel<C>(va + v * C, vo + v * C);
+        }
+#pragma unroll
+        for (int i = 0; i < C; ++i)
+            reinterpret_cast<float4*>(out)[q * C + i] = make_float4(vo[4 * i], vo[4 * i + 1], vo[4 * i + 2], vo[4 * i + 3]);
+    }
+    // the remaining voxels (all of them when !VEC), one per thread
+    const long long first = 4 * nq;
+    const long long start = VEC ? (blockIdx.x == 0 ? first + threadIdx.x : nvox) : (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long step = VEC ? blockDim.x : (long long)gridDim.x * blockDim.x;
+    for (long long v = start; v < nvox; v += step) {
+        if (BWD) gs_bwd_voxel<C>(a + v * C, g + v * C, out + v * C);
+        else gs_fwd_voxel<C>(a + v * C, out + v * C);
+    }
+}
+
+// entropy of the 2-class gambling softmax at one voxel; dH/dl when `dl` is given
+template <bool FAST>
+__device__ __forceinline__ float gambling_entropy2(float l0, float l1, float* dl) {
+    const float e0 = fexp<FAST>(l0), e1 = fexp<FAST>(l1);
+    const float den = e0 + e1 + 1e-18f;
+    const float p0 = fdiv<FAST>(e0, den), p1 = fdiv<FAST>(e1, den);
+    const float lg0 = flog<FAST>(p0 + 1e-6f), lg1 = flog<FAST>(p1 + 1e-6f);
+    if (dl) {   // dH/dp_c = -(log(p_c + 1e-6) + p_c / (p_c + 1e-6));  dH/dl_j = p_j (h_j - sum_c h_c p_c)
+        const float h0 = -(lg0 + fdiv<FAST>(p0, p0 + 1e-6f)), h1 = -(lg1 + fdiv<FAST>(p1, p1 + 1e-6f));
+        const float s = h0 * p0 + h1 * p1;
+        dl[0] = p0 * (h0 - s);
+        dl[1] = p1 * (h1 - s);
+    }
+    return -(p0 * lg0 + p1 * lg1);
+}
+
+// one thread per patch: u[b, n] (forward) or g_logits += gu[b, n] / 8 * dH/dl at the patch's 8 voxels (BWD)
+template <bool FAST, bool BWD>
+__global__ __launch_bounds__(256) void gambling_uncertainty_kernel(const float2* __restrict__ L, int B, int D, int H, int W, int kd, int kh,
+                                                                   int kw, float* __restrict__ u, const float* __restrict__ gu,
+                                                                   float2* __restrict__ gL) {
+    const int Dp = D / kd, Hp = H / kh, Wp = W / kw;
+    const long long N = (long long)Dp * Hp * Wp, total = (long long)B * N;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const long long b = t / N;
+        const int n = (int)(t - b * N);
+        const int pd = n / (Hp * Wp), ph = (n / Wp) % Hp, pw = n % Wp;
+        const int d0 = kd * pd + kd / 2 - 1, h0 = kh * ph + kh / 2 - 1, w0 = kw * pw + kw / 2 - 1;
+        const float g8 = BWD ? gu[t] * 0.125f : 0.f;
+        float s = 0.f;
+#pragma unroll
+        for (int dd = 0; dd < 2; ++dd)
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                for (int ww = 0; ww < 2; ++ww) {
+                    const long long v = ((b * D + d0 + dd) * H + h0 + hh) * W + w0 + ww;
+                    const float2 l = L[v];
+                    if (BWD) {
+                        float dl[2];
+                        gambling_entropy2<FAST>(l.x, l.y, dl);
+                        float2 g = gL[v];
+                        g.x += g8 * dl[0];
+                        g.y += g8 * dl[1];
+                        gL[v] = g;
+                    } else {
+                        s += gambling_entropy2<FAST>(l.x, l.y, nullptr);
+                    }
+                }
+        if (!BWD) u[t] = s * 0.125f;
+    }
+}
+
+// One workgroup, fixed summation order: r_i = (sum_z rsl[z][i]) / (cnt_i - 1 + 1e-18); out[0] = sum_i r_i u_i; the gradient pass's row
+// weights kappa_i (wk) and kappa_i H_i partials (wh), written by passes 1-3 with u = 1, are scaled by u_i in place; gu_i = coef[0] r_i / BN.
+constexpr int GF_THREADS = 1024;
+__global__ __launch_bounds__(GF_THREADS) void fecl_gambling_finalize_kernel(const float* __restrict__ u, const float* __restrict__ coef,
+                                                                            long long BN, int CS, float* __restrict__ ws,
+                                                                            const float* __restrict__ rsl, double* __restrict__ out,
+                                                                            float* __restrict__ r, float* __restrict__ gu) {
+    __shared__ double red[GF_THREADS / 64];
+    const float* wc = ws + 2LL * CS * BN;
+    float* wh = ws + 3LL * CS * BN;
+    float* wk = ws + 4LL * CS * BN;
+    const float gscale = coef ? coef[0] / (float)BN : 0.f;
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < BN; i += GF_THREADS) {
+        float ph = rsl[i], cnt = wc[i];
+        for (int z = 1; z < CS; ++z) { ph += rsl[z * BN + i]; cnt += wc[z * BN + i]; }
+        const float ri = ph / (cnt - 1.f + 1e-18f), ui = u[i];
+        acc += (double)(ri * ui);
+        wk[i] *= ui;
+        for (int z = 0; z < CS; ++z) wh[z * BN + i] *= ui;
+        if (r) r[i] = ri;
+        if (gu) gu[i] = gscale * ri;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < GF_THREADS / 64; ++w) s += red[w];
+        out[0] = s;
+    }
+}
+
+__global__ void scale_rows_kernel(const float* __restrict__ r, const float* __restrict__ coef, long long n, float* __restrict__ gu) {
+    const float sc = coef[0] / (float)n;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) gu[i] = sc * r[i];
+}
+
+template <bool BWD>
+static int gambling_softmax_launch(const float* a, const float* g, float* out, long long nvox, int C, dycon_stream_t stream) {
+    const bool vec = (((uintptr_t)a | (uintptr_t)g | (uintptr_t)out) & 15) == 0;
+    const int grid = lgrid(vec ? nvox / 4 + 1 : nvox);
+    switch (C) {
+#define GS_CASE(K)                                                                                                \
+    case K:                                                                                                       \
+        if (vec) gambling_softmax_kernel<K, BWD, true><<<grid, 256, 0, stream>>>(a, g, out, nvox);                \
+        else gambling_softmax_kernel<K, BWD, false><<<grid, 256, 0, stream>>>(a, g, out, nvox);                   \
+        break;
+        GS_CASE(1) GS_CASE(2) GS_CASE(3) GS_CASE(4) GS_CASE(5) GS_CASE(6) GS_CASE(7) GS_CASE(8)
+#undef GS_CASE
+    }
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_gambling_softmax_fwd(const float* x, float* y, long long nvox, int C, dycon_stream_t stream) {
+    DYCON_REQUIRE(x && y && nvox > 0 && C >= 1 && C <= 8, "gambling_softmax_fwd: bad arguments (C in 1..8)");
+    return gambling_softmax_launch<false>(x, nullptr, y, nvox, C, stream);
+}
+
+extern "C" int dycon_gambling_softmax_bwd(const float* y, const float* gy, float* gx, long long nvox, int C, dycon_stream_t stream) {
+    DYCON_REQUIRE(y && gy && gx && nvox > 0 && C >= 1 && C <= 8, "gambling_softmax_bwd: bad arguments (C in 1..8)");
+    return gambling_softmax_launch<true>(y, gy, gx, nvox, C, stream);
+}
+
+static int gambling_check(const char* who, const float* logits, int B, int D, int H, int W, int kd, int kh, int kw) {
+    DYCON_REQUIRE(logits && B > 0 && kd > 0 && kh > 0 && kw > 0, "%s: bad arguments", who);
+    DYCON_REQUIRE(kd % 2 == 0 && kh % 2 == 0 && kw % 2 == 0, "%s: the patch factor must be even per axis (got %d, %d, %d)", who, kd, kh, kw);
+    DYCON_REQUIRE(D >= kd && H >= kh && W >= kw, "%s: volume smaller than one patch", who);
+    return DYCON_OK;
+}
+
+extern "C" int dycon_gambling_uncertainty_fwd(const float* logits, int B, int D, int H, int W, int kd, int kh, int kw, float* u, int fast,
+                                              dycon_stream_t stream) {
+    if (int e = gambling_check("gambling_uncertainty_fwd", logits, B, D, H, W, kd, kh, kw)) return e;
+    DYCON_REQUIRE(u, "gambling_uncertainty_fwd: null output");
+    const long long total = (long long)B * (D / kd) * (H / kh) * (W / kw);
+    if (fast)
+        gambling_uncertainty_kernel<true, false><<<lgrid(total), 256, 0, stream>>>((const float2*)logits, B, D, H, W, kd, kh, kw, u, nullptr, nullptr);
+    else
+        gambling_uncertainty_kernel<false, false><<<lgrid(total), 256, 0, stream>>>((const float2*)logits, B, D, H, W, kd, kh, kw, u, nullptr, nullptr);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_gambling_uncertainty_bwd(const float* logits, int B, int D, int H, int W, int kd, int kh, int kw, const float* gu,
+                                              float* g_logits, int fast, dycon_stream_t stream) {
+    if (int e = gambling_check("gambling_uncertainty_bwd", logits, B, D, H, W, kd, kh, kw)) return e;
+    DYCON_REQUIRE(gu && g_logits, "gambling_uncertainty_bwd: null pointer");
+    const long long total = (long long)B * (D / kd) * (H / kh) * (W / kw);
+    if (fast)
+        gambling_uncertainty_kernel<true, true><<<lgrid(total), 256, 0, stream>>>((const float2*)logits, B, D, H, W, kd, kh, kw, nullptr, gu, (float2*)g_logits);
+    else
+        gambling_uncertainty_kernel<false, true><<<lgrid(total), 256, 0, stream>>>((const float2*)logits, B, D, H, W, kd, kh, kw, nullptr, gu, (float2*)g_logits);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+// the column split of the kernel family dycon_fecl_fwd_rows selects (focal off)
+static int fecl_rows_splits(int dtype, int B, int N, int Dm) {
+    int CS, tps;
+    fecl_split(B, N, fecl_rows128_ok(dtype, B, N, Dm, 2.f, 0), CS, tps);
+    return CS;
+}
+
+extern "C" size_t dycon_fecl_rows_workspace(int B, int N, int Dm) {
+    int CS, CS2, tps;
+    fecl_split(B, N, false, CS, tps);
+    fecl_split(B, N, true, CS2, tps);
+    if (CS2 > CS) CS = CS2;
+    return (size_t)CS * B * N * sizeof(float);
+}
+
+extern "C" int dycon_fecl_fwd_rows(const void* feat, const void* teacher, const float* mask, float* rows, int dtype, int B, int N, int Dm,
+                                   float temperature, float cross_thresh, double* out, float* workspace, size_t ws_bytes,
+                                   size_t rows_bytes, dycon_stream_t stream) {
+    if (int e = fecl_check("fecl_fwd_rows", feat, mask, B, N, Dm, temperature, ws_bytes)) return e;
+    DYCON_REQUIRE(out && workspace && rows, "fecl_fwd_rows: null pointer");
+    DYCON_REQUIRE(rows_bytes >= dycon_fecl_rows_workspace(B, N, Dm), "fecl_fwd_rows: row-term buffer too small");
+    if (hipMemsetAsync(out, 0, 4 * sizeof(double), stream) != hipSuccess) { dycon_set_error("fecl_fwd_rows: memset failed"); return DYCON_ERR_LAUNCH; }
+    int e = DYCON_OK;
+    if (fecl_rows128_ok(dtype, B, N, Dm, 2.f, 0)) {
+        e = fecl_rows128_launch<1>(feat, nullptr, mask, nullptr, B, N, Dm, temperature, 0, cross_thresh, workspace, out, stream);
+        if (!e) e = fecl_rows128_launch<2>(feat, nullptr, mask, nullptr, B, N, Dm, temperature, 0, cross_thresh, workspace, out, stream);
+        if (!e) e = fecl_rows128_launch<3>(feat, teacher, mask, nullptr, B, N, Dm, temperature, 0, cross_thresh, workspace, out, stream, rows);
+    } else
+    DYCON_DISPATCH(dtype, {
+        e = fecl_launch<T, 1>(feat, nullptr, mask, nullptr, B, N, Dm, temperature, 0.f, 0, cross_thresh, workspace, out, nullptr, 1.f, stream);
+        if (!e) e = fecl_launch<T, 2>(feat, nullptr, mask, nullptr, B, N, Dm, temperature, 0.f, 0, cross_thresh, workspace, out, nullptr, 1.f, stream);
+        if (!e) e = fecl_launch<T, 3>(feat, teacher, mask, nullptr, B, N, Dm, temperature, 0.f, 0, cross_thresh, workspace, out, nullptr, 1.f, stream, rows);
+    });
+    return e;
+}
+
+extern "C" int dycon_fecl_gambling_finalize(const float* u, const float* coef, int dtype, int B, int N, int Dm, double* out, float* r,
+                                            float* gu, float* workspace, size_t ws_bytes, const float* rows, size_t rows_bytes,
+                                            dycon_stream_t stream) {
+    DYCON_REQUIRE(u && out && workspace && rows && B > 0 && N > 0 && (!gu || coef), "fecl_gambling_finalize: bad arguments");
+    DYCON_REQUIRE(ws_bytes >= dycon_fecl_workspace(B, N, Dm), "fecl_gambling_finalize: workspace too small");
+    DYCON_REQUIRE(rows_bytes >= (size_t)fecl_rows_splits(dtype, B, N, Dm) * B * N * sizeof(float), "fecl_gambling_finalize: row-term buffer too small");
+    fecl_gambling_finalize_kernel<<<1, GF_THREADS, 0, stream>>>(u, coef, (long long)B * N, fecl_rows_splits(dtype, B, N, Dm), workspace, rows,
+                                                                out, r, gu);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_fecl_gambling_grad(const float* r, const float* coef, long long n, float* gu, dycon_stream_t stream) {
+    DYCON_REQUIRE(r && coef && gu && n > 0, "fecl_gambling_grad: bad arguments");
+    scale_rows_kernel<<<lgrid(n), 256, 0, stream>>>(r, coef, n, gu);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }

@@ -730,7 +730,7 @@ def mask_pool(labels, k):
 
 
 class FeclState:
-    __slots__ = ("out", "ws", "loss")
+    __slots__ = ("out", "ws", "loss", "rows")
 
 
 def fecl_fwd(feat, teacher, mask, gambling, temperature, gamma, use_focal, cross_thresh, lambda_cross, out=None):
@@ -762,6 +762,106 @@ def fecl_bwd(feat, teacher, mask, gambling, temperature, gamma, use_focal, cross
     call("dycon_fecl_bwd", _p(feat), _p(teacher), _p(mask), _p(gambling), dt(feat), B, N, Dm, temperature, gamma,
          int(use_focal), cross_thresh, lambda_cross, _p(st.out), _p(coef), _p(g), _p(st.ws), st.ws.numel() * 4, _s())
     return g
+
+
+# ------------------------------------------------------------------ gambling-softmax uncertainty (utils/dycon_losses.py:14-26, :209-211)
+def _gambling_channels(x):
+    if x.dtype != torch.float32 or x.dim() < 1 or not 1 <= x.shape[-1] <= 8:
+        raise ValueError(f"gambling_softmax: expected fp32 (..., C) with C in 1..8, got {tuple(x.shape)} {x.dtype}")
+
+
+def gambling_softmax(x):
+    """x (B, ..., C) channels-last fp32, C in 1..8 -> exp(x) / (sum_c exp(x_c) + 1e-18), no max shift (dycon_losses.py:14-26)"""
+    _gambling_channels(x)
+    y = torch.empty_like(x)
+    call("dycon_gambling_softmax_fwd", _p(x), _p(y), x.numel() // x.shape[-1], x.shape[-1], _s())
+    return y
+
+
+def gambling_softmax_bwd(y, gy):
+    _gambling_channels(y)
+    if gy.shape != y.shape or gy.dtype != torch.float32:
+        raise ValueError("gambling_softmax_bwd: gy must match y (fp32)")
+    gx = torch.empty_like(y)
+    call("dycon_gambling_softmax_bwd", _p(y), _p(gy), _p(gx), y.numel() // y.shape[-1], y.shape[-1], _s())
+    return gx
+
+
+def _gambling_k(k):
+    kd, kh, kw = (k, k, k) if isinstance(k, int) else tuple(int(v) for v in k)
+    if kd % 2 or kh % 2 or kw % 2:
+        raise ValueError(f"gambling uncertainty: the patch factor must be even per axis, got {(kd, kh, kw)}")
+    return kd, kh, kw
+
+
+def _gambling_logits(logits, k):
+    if logits.dim() != 5 or logits.shape[-1] != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"gambling uncertainty: expected fp32 logits (B, D, H, W, 2), got {tuple(logits.shape)} {logits.dtype}")
+    kd, kh, kw = _gambling_k(k)
+    B, D, H, W, _ = logits.shape
+    if D < kd or H < kh or W < kw:
+        raise ValueError(f"gambling uncertainty: volume {(D, H, W)} smaller than one patch {(kd, kh, kw)}")
+    return B, D, H, W, kd, kh, kw
+
+
+def gambling_uncertainty(logits, k, fast=False, out=None):
+    """logits (B, D, H, W, 2) fp32 -> u (B, N): the entropy of the gambling softmax, trilinearly downsampled by 1/k
+    (train_DyCON_Pancreas.py:242-246); k an even int or (kd, kh, kw)."""
+    B, D, H, W, kd, kh, kw = _gambling_logits(logits, k)
+    N = (D // kd) * (H // kh) * (W // kw)
+    if out is not None and (out.dtype != torch.float32 or out.numel() != B * N):
+        raise ValueError(f"gambling_uncertainty: out must hold B*N = {B * N} fp32 values")
+    u = out if out is not None else torch.empty((B, N), dtype=torch.float32, device=logits.device)
+    call("dycon_gambling_uncertainty_fwd", _p(logits), B, D, H, W, kd, kh, kw, _p(u), int(fast), _s())
+    return u
+
+
+def gambling_uncertainty_bwd(logits, k, gu, g_logits, fast=False):
+    """g_logits += gu * du/dlogits, in place (the 8 voxels of each patch)"""
+    B, D, H, W, kd, kh, kw = _gambling_logits(logits, k)
+    if gu.dtype != torch.float32 or gu.numel() != B * (D // kd) * (H // kh) * (W // kw):
+        raise ValueError(f"gambling_uncertainty_bwd: gu must hold B*N fp32 values, got {tuple(gu.shape)} {gu.dtype}")
+    if g_logits.shape != logits.shape or g_logits.dtype != torch.float32:
+        raise ValueError(f"gambling_uncertainty_bwd: g_logits must match the logits, got {tuple(g_logits.shape)} {g_logits.dtype}")
+    call("dycon_gambling_uncertainty_bwd", _p(logits), B, D, H, W, kd, kh, kw, _p(gu), _p(g_logits), int(fast), _s())
+    return g_logits
+
+
+def fecl_fwd_rows(feat, teacher, mask, temperature, cross_thresh, out=None):
+    """FeCL passes with u = 1 and no focal weight, keeping the per-row student terms for fecl_gambling_finalize.  Returns the state
+    (st.rows: the row-term partials); st.out[0] is meaningless until the finalize."""
+    B, N, Dm = feat.shape
+    st = FeclState()
+    st.out = out if out is not None else torch.empty(4, dtype=torch.float64, device=feat.device)
+    st.loss = torch.empty(1, dtype=torch.float32, device=feat.device)
+    st.ws = _ws(query("dycon_fecl_workspace", B, N, Dm), feat)
+    st.rows = _ws(query("dycon_fecl_rows_workspace", B, N, Dm), feat)
+    call("dycon_fecl_fwd_rows", _p(feat), _p(teacher), _p(mask), _p(st.rows), dt(feat), B, N, Dm, temperature, cross_thresh,
+         _p(st.out), _p(st.ws), st.ws.numel() * 4, st.rows.numel() * 4, _s())
+    return st
+
+
+def fecl_gambling_finalize(feat, st, u, coef=None, want_r=False):
+    """Weight the student term by u (B, N): st.out[0] = sum r*u, gradient-pass row weights scaled by u.  Returns (r, gu): r when
+    want_r, gu = coef[0] * r / (B*N) when coef is given (else None)."""
+    B, N, Dm = feat.shape
+    r = torch.empty((B, N), dtype=torch.float32, device=feat.device) if want_r else None
+    gu = torch.empty((B, N), dtype=torch.float32, device=feat.device) if coef is not None else None
+    if u.dtype != torch.float32 or u.numel() != B * N:
+        raise ValueError(f"fecl_gambling_finalize: u must hold B*N = {B * N} fp32 values, got {tuple(u.shape)} {u.dtype}")
+    if coef is not None and (coef.dtype != torch.float32 or coef.numel() < 1):
+        raise ValueError("fecl_gambling_finalize: coef must be fp32")
+    call("dycon_fecl_gambling_finalize", _p(u), _p(coef), dt(feat), B, N, Dm, _p(st.out), _p(r), _p(gu), _p(st.ws), st.ws.numel() * 4,
+         _p(st.rows), st.rows.numel() * 4, _s())
+    return r, gu
+
+
+def fecl_gambling_grad(r, coef):
+    if r.dtype != torch.float32 or coef.dtype != torch.float32 or coef.numel() < 1:
+        raise ValueError("fecl_gambling_grad: r and coef must be fp32")
+    gu = torch.empty_like(r)
+    call("dycon_fecl_gambling_grad", _p(r), _p(coef), r.numel(), _p(gu), _s())
+    return gu
 
 
 def similarity_histograms(feat, mask, tau=0.6, bins=50):

@@ -55,6 +55,8 @@ class TrainConfig:
     l_weight: float = 1.0
     u_weight: float = 0.5
     use_focal: int = 1
+    use_gambling: int = 0               # FeCL positives weighted by the gambling-softmax entropy of the student's logits, differentiably
+                                        # (the commented call sites of train_DyCON_Pancreas.py:242-246, :252; focal result then discarded)
     use_teacher_loss: int = 1
     feature_scaler: int = 2
     seed: int = 1337
@@ -375,6 +377,8 @@ class DyconTrainer:
         for name in ("dycon_fecl_fwd", "dycon_fecl_bwd"):
             for e in by.get(name, ()):
                 e[1][11] = thr
+        for e in by.get("dycon_fecl_fwd_rows", ()):
+            e[1][9] = thr
         for e in by.get("dycon_step_losses", ()):
             e[1][10] = float(cw)
         for e in by.get("dycon_set_scalars", ()):           # coef = (l_w, l_w*(1-dk)*gw, l_w*dk*gw, cw, u_w, u_w): only cw moves
@@ -515,6 +519,10 @@ class DyconTrainer:
         # the step's 16 + 4 loss accumulators live in ONE buffer: a data-parallel run exchanges them with one all-reduce
         sums, fo = self.acc20[:16], self.acc20[16:]
         ops.seg_losses_fwd(s_logits, t_logits, label, LB, beta, fast=self._fast_math, out=sums)
+        k = (D // s_feat.shape[1], H // s_feat.shape[2], W // s_feat.shape[3])     # patch size per axis of the feature grid
+        gmb = bool(c.use_gambling)
+        if gmb:   # u = interpolate(entropy(gambling_softmax(stud_logits)), 1/k) (Pancreas :242-246), on main beside the feature branch
+            u = ops.gambling_uncertainty(s_logits, k, fast=self._fast_math)
         fctx = (lambda: ops.on_stream(self.feat)) if self.feat is not None else contextlib.nullcontext
         with fctx():
             if self.feat is not None:                     # teacher features (the student's head was enqueued on self.feat)
@@ -531,16 +539,23 @@ class DyconTrainer:
                 t_feat.record_stream(self.feat)
             s_emb, s_nrm = ops.l2norm_fwd(s_feat.reshape(B, -1, s_feat.shape[-1]))          # :316-319
             t_emb, _ = ops.l2norm_fwd(t_feat.reshape(B, -1, t_feat.shape[-1]))              # :321-323
-            k = (D // s_feat.shape[1], H // s_feat.shape[2], W // s_feat.shape[3])
             mask = ops.mask_pool(label, k)                                                   # :326-330
             teacher_emb = t_emb if c.use_teacher_loss else None
-            fargs = (s_emb, teacher_emb, mask, None, c.temp, c.gamma, bool(c.use_focal), thr)
-            f_loss, fst = ops.fecl_fwd(*fargs, 1.0, out=fo)
+            if gmb:    # passes 1-3 with u = 1 (u is not needed before the finalize below): the per-row student terms are kept
+                fargs = (s_emb, teacher_emb, mask, None, c.temp, c.gamma, False, thr)
+                fst = ops.fecl_fwd_rows(s_emb, teacher_emb, mask, c.temp, thr, out=fo)
+            else:
+                fargs = (s_emb, teacher_emb, mask, None, c.temp, c.gamma, bool(c.use_focal), thr)
+                f_loss, fst = ops.fecl_fwd(*fargs, 1.0, out=fo)
             self._mark("fecl_fwd_end")
         if self.feat is not None:
             ops.fork(feat, main)       # the scalar loss (and the DDP exchange below) needs the FeCL sums
-            for t in (t_feat, mask):
+            for t in (t_feat, mask) + ((fst.ws, fst.rows) if gmb else ()):
                 t.record_stream(main)
+        if gmb:
+            # the student term sum r*u into fo[0] (before the DDP exchange), u folded into the gradient pass's row weights,
+            # gu = coef_fecl * r / (B*N): the FeCL student part's d/du with the scaling of its feature gradient
+            _, gu = ops.fecl_gambling_finalize(s_emb, fst, u, coef=self.coef[5:6])
         if glob:
             # Dice is a ratio of batch-GLOBAL sums (losses.py:11-14) and the FeCL cross branch a global sum over a
             # global count (dycon_losses.py:229): exchange the 16 + 4 accumulators (one collective), then finalise on every rank
@@ -556,8 +571,10 @@ class DyconTrainer:
         # ---- backward (:364-365); coef was written at the head of the step
         self._mark("loss_end")
         g_logits = ops.seg_losses_bwd(s_logits, t_logits, label, LB, beta, sums, self.coef, cons_kind, fast=self._fast_math)
-        if self.feat is not None and (glob or os.environ.get("DYCON_FEAT_BWD_EARLY", "0") != "1"):
-            ops.fork(main, feat)       # DDP: the all-reduced FeCL sums (cross-branch count) are exchanged on main
+        if gmb:    # FeCL's gradient into the student's logits through u (the 8 voxels of each patch), before the backward reads g_logits
+            ops.gambling_uncertainty_bwd(s_logits, k, gu, g_logits, fast=self._fast_math)
+        if self.feat is not None and (glob or gmb or os.environ.get("DYCON_FEAT_BWD_EARLY", "0") != "1"):
+            ops.fork(main, feat)       # DDP: the all-reduced FeCL sums (cross-branch count) are exchanged on main; gambling: the finalize
         with fctx():
             if "feat_bwd" in ABLATE:     # tools/ablate.py (timing only): the feature branch's loss backward switched off
                 g_feat = torch.zeros_like(s_feat)

@@ -19,6 +19,30 @@ def adaptive_beta(epoch, total_epochs, max_beta=5.0, min_beta=0.5):
     return max_beta * ((min_beta / max_beta) ** (epoch / total_epochs))
 
 
+class _GamblingSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits):
+        x = logits.movedim(1, -1).contiguous().float()
+        y = ops.gambling_softmax(x)
+        ctx.save_for_backward(y)
+        ctx.in_dtype = logits.dtype
+        return y.movedim(-1, 1).to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        gx = ops.gambling_softmax_bwd(y, g.movedim(1, -1).contiguous().float())
+        return gx.movedim(-1, 1).to(ctx.in_dtype)
+
+
+def gambling_softmax(logits):
+    """dycon_losses.py:14-26: exp(logits) / (sum over dim 1 + 1e-18), NO max shift (logits above ~88.7 give NaN, as there).
+    (B, C, ...) with C in 1..8, differentiable."""
+    if logits.dim() < 2 or not 1 <= logits.shape[1] <= 8:
+        raise ValueError(f"gambling_softmax: expected (B, C, ...) with C in 1..8, got {tuple(logits.shape)}")
+    return _GamblingSoftmax.apply(logits)
+
+
 def sigmoid_rampup(current_epoch, total_rampup_epochs, min_threshold, max_threshold, steepness=5.0):
     """dycon_losses.py:28-47 (threshold schedule of FeCL)."""
     if total_rampup_epochs == 0:
@@ -84,6 +108,35 @@ class _FeCLFunction(torch.autograd.Function):
         return (gf.to(ctx.in_dtype),) + (None,) * 8
 
 
+class _FeCLGamblingFunction(torch.autograd.Function):
+    """FeCL with a differentiable uncertainty weight u (dycon_losses.py:209-211): the student term is mean(r * u) with
+    r_i = sum_j ell_ij / (cnt_i - 1 + 1e-18) (the focal result is discarded), so d/du_i = g * r_i / (B*N)."""
+
+    @staticmethod
+    def forward(ctx, feat, teacher, mask, gambling, temperature, gamma, thr, lambda_cross):
+        f = feat.contiguous()
+        if f.dtype not in (torch.float32, torch.bfloat16):
+            f = f.float()
+        B, N = f.shape[0], f.shape[1]
+        t = teacher.contiguous().to(f.dtype) if teacher is not None else None
+        m = mask.reshape(B, N).contiguous().float()
+        u = gambling.reshape(B, N).contiguous().float()
+        st = ops.fecl_fwd_rows(f, t, m, float(temperature), float(thr))
+        r, _ = ops.fecl_gambling_finalize(f, st, u, want_r=True)
+        loss = ops.fecl_finalize(st, B * N, float(lambda_cross), t is not None)
+        ctx.args = (f, t, m, None, float(temperature), float(gamma), False, float(thr), float(lambda_cross))
+        ctx.st, ctx.r, ctx.in_dtype, ctx.u_meta = st, r, feat.dtype, (gambling.shape, gambling.dtype)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        coef = g.reshape(1).float().contiguous()
+        gf = ops.fecl_bwd(*ctx.args, ctx.st, coef)
+        gu = ops.fecl_gambling_grad(ctx.r, coef)
+        shape, dtype = ctx.u_meta
+        return gf.to(ctx.in_dtype), None, None, gu.reshape(shape).to(dtype), None, None, None, None
+
+
 class FeCLoss(nn.Module):
     """Focal patch-contrastive loss (dycon_losses.py:120-235); same constructor and call signature."""
 
@@ -94,5 +147,8 @@ class FeCLoss(nn.Module):
 
     def forward(self, feat, mask, teacher_feat=None, gambling_uncertainty=None, epoch=0):
         thr = sigmoid_rampup(epoch, self.rampup_epochs, min_threshold=0.3, max_threshold=0.5)
+        if gambling_uncertainty is not None and gambling_uncertainty.requires_grad:   # u from the logits, not detached (Pancreas :242-246)
+            return _FeCLGamblingFunction.apply(feat, teacher_feat.detach() if teacher_feat is not None else None, mask,
+                                               gambling_uncertainty, self.temperature, self.gamma, thr, self.lambda_cross)
         return _FeCLFunction.apply(feat, teacher_feat.detach() if teacher_feat is not None else None, mask,
                                    gambling_uncertainty, self.temperature, self.gamma, self.use_focal, thr, self.lambda_cross)

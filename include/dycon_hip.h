@@ -382,6 +382,36 @@ int dycon_fecl_bwd(const void* feat, const void* teacher, const float* mask, con
                    float cross_thresh, float lambda_cross, const double* out, const float* coef,
                    void* g_feat, float* workspace, size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- gambling-softmax uncertainty
+ * (utils/dycon_losses.py:14-26 gambling_softmax, :209-211 the weighted student term; train_DyCON_Pancreas.py:242-246 the producer)
+ * p = exp(l) / (sum_c exp(l_c) + 1e-18) with NO max shift (a logit above ~88.7 gives NaN, as in the reference).
+ * x, y, gy, gx: (B, V, C) channels-last fp32, nvox = B*V, C in 1..8.  gx = dL/dx given gy = dL/dy and y = p. */
+int dycon_gambling_softmax_fwd(const float* x, float* y, long long nvox, int C, dycon_stream_t stream);
+int dycon_gambling_softmax_bwd(const float* y, const float* gy, float* gx, long long nvox, int C, dycon_stream_t stream);
+/* u[b, n] = F.interpolate(H, scale_factor=1/k, trilinear, align_corners=False), H = -sum_c p_c log(p_c + 1e-6) of the 2-class
+ * gambling softmax of logits (B, D, H, W, 2) fp32; k even per axis, n over the (D/kd, H/kh, W/kw) grid.  With an even k, u is the
+ * mean of H over the 2x2x2 voxels {k i + k/2 - 1, k i + k/2} per axis.  fast: hardware exp / log / rcp (bf16 step).
+ * _bwd ADDS gu[b, n] * du/dlogits into g_logits (same layout), touching the 8 voxels of each patch only. */
+int dycon_gambling_uncertainty_fwd(const float* logits, int B, int D, int H, int W, int kd, int kh, int kw, float* u,
+                                   int fast, dycon_stream_t stream);
+int dycon_gambling_uncertainty_bwd(const float* logits, int B, int D, int H, int W, int kd, int kh, int kw,
+                                   const float* gu, float* g_logits, int fast, dycon_stream_t stream);
+/* FeCL with the uncertainty weight (utils/dycon_losses.py:209-211: focal result discarded, student term = mean(r * u)).
+ * _fwd_rows: passes 1-3 of dycon_fecl_fwd with u = 1 and no focal weight, plus the per-row partial sums of sum_j ell_ij into
+ * `rows` ([column split][B*N], dycon_fecl_rows_workspace bytes).  It does not write a loss.
+ * _gambling_finalize (once u is known): r_i = sum_j ell_ij / (cnt_i - 1 + 1e-18) in a fixed order, out[0] = sum_i r_i u_i
+ * (what dycon_step_losses / dycon_fecl_finalize read; u, r, gu hold B*N floats, rows is what _fwd_rows wrote), the gradient pass's row weights scaled by u in the workspace, and optionally
+ * r (B*N) and gu = coef[0] * r / (B*N) = coef[0] * d(student term)/du.  Then dycon_fecl_bwd(gambling=NULL, use_focal=0) gives the
+ * feature gradient.  _gambling_grad: gu = coef[0] * r / n. */
+size_t dycon_fecl_rows_workspace(int B, int N, int Dm);
+int dycon_fecl_fwd_rows(const void* feat, const void* teacher, const float* mask, float* rows, int dtype, int B, int N,
+                        int Dm, float temperature, float cross_thresh, double* out, float* workspace, size_t ws_bytes,
+                        size_t rows_bytes, dycon_stream_t stream);
+int dycon_fecl_gambling_finalize(const float* u, const float* coef, int dtype, int B, int N, int Dm, double* out, float* r,
+                                 float* gu, float* workspace, size_t ws_bytes, const float* rows, size_t rows_bytes,
+                                 dycon_stream_t stream);
+int dycon_fecl_gambling_grad(const float* r, const float* coef, long long n, float* gu, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- optimiser (train_DyCON_BraTS19.py:155-164,268,369-372)
  * sumsq[0] += sum g^2 (double, caller zeroes) -> clip_grad_norm_; then one fused pass:
  *   coef = min(1, max_norm/(sqrt(sumsq)+1e-6)); g = coef*g + wd*p; m = mu*m + g; p -= lr*m   on [0,n_sgd)
