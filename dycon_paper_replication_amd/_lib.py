@@ -86,6 +86,16 @@ SIGNATURES = {
     "dycon_softmax_kl_bwd": (I, [P, P, L, I, L, I, I, P, P, P]),
     "dycon_dice_fwd": (I, [P, P, I, I, L, I, L, I, P, F, P, P, P]),
     "dycon_dice_bwd": (I, [P, P, I, I, L, I, L, I, P, F, P, P, P, P]),
+    "dycon_dice1_fwd": (I, [P, P, I, L, I, L, I, P, P, P]),
+    "dycon_dice1_bwd": (I, [P, P, I, L, I, L, I, P, P, P, P]),
+    "dycon_entropy_fwd": (I, [P, L, I, L, F, P, P, P, P]),
+    "dycon_entropy_bwd": (I, [P, L, I, L, F, P, P, P, P]),
+    "dycon_sym_mse_fwd": (I, [P, P, L, P, P, P]),
+    "dycon_sym_mse_bwd": (I, [P, P, L, P, P, P]),
+    "dycon_kl_rows_fwd": (I, [P, L, P, L, L, L, L, I, P, P, P]),
+    "dycon_kl_rows_bwd": (I, [P, L, P, L, L, L, L, I, P, P, L, P]),
+    "dycon_focal_fwd": (I, [P, P, I, L, I, L, F, P, I, P, P, P]),
+    "dycon_focal_bwd": (I, [P, P, I, L, I, L, F, P, I, P, P, P]),
     "dycon_l2norm_fwd": (I, [P, P, P, I, L, I, F, P]),
     "dycon_l2norm_bwd": (I, [P, P, P, P, I, L, I, F, P]),
     "dycon_mask_pool": (I, [P, I, P, I, I, I, I, I, I, I, P]),

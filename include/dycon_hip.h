@@ -353,6 +353,46 @@ int dycon_dice_bwd(const dycon_view_t* score, const dycon_view_t* target, int ta
                    long long V, int softmax, const float* weights_host, float n_div, const double* sums, const float* g_up,
                    const dycon_view_t* grad, dycon_stream_t stream);
 
+/* losses.dice_loss1(score, target) (utils/losses.py:19-27; softmax = 0, C = 1, target of the score's shape, any target_kind) and
+ * losses.softmax_dice_loss(a, b) (utils/losses.py:39-56; softmax = 1: both views are logits, float32, and the softmax over the C
+ * channels is taken inside):  out[0] = mean_c 1 - (2 sum s_c t_c + 1e-5) / (sum s_c + sum t_c + 1e-5), PLAIN sums over the whole
+ * view.  sums: 24 doubles of scratch, kept for the backward. */
+int dycon_dice1_fwd(const dycon_view_t* score, const dycon_view_t* target, int target_kind, long long n, int C, long long V,
+                    int softmax, double* sums, float* out, dycon_stream_t stream);
+/* grad = g_up[0] * d out / d a, the FIRST argument; the denominators are symmetric, so (b, a) with the same sums gives the second */
+int dycon_dice1_bwd(const dycon_view_t* a, const dycon_view_t* b, int b_kind, long long n, int C, long long V, int softmax,
+                    const double* sums, const float* g_up, const dycon_view_t* grad, dycon_stream_t stream);
+/* H = -sum_c p_c log(p_c + 1e-6) over the C channels.  map != NULL: map[n V + v] = scale * H (losses.entropy_map, utils/losses.py:202-205;
+ * entropy_loss_map, :59-62, with scale = 1 / log C); else out[0] = scale * mean H (entropy_minmization, :195-199; entropy_loss, :30-36)
+ * with sum one double of scratch (zeroed by the call). */
+int dycon_entropy_fwd(const dycon_view_t* p, long long n, int C, long long V, float scale, float* map, double* sum, float* out,
+                      dycon_stream_t stream);
+/* grad = d (sum g_map * map) / d p (g_map: n V floats) or g_up[0] * d out / d p; exactly one of g_map, g_up is non-NULL */
+int dycon_entropy_bwd(const dycon_view_t* p, long long n, int C, long long V, float scale, const float* g_map, const float* g_up,
+                      const dycon_view_t* grad, dycon_stream_t stream);
+/* losses.symmetric_mse_loss(a, b) (utils/losses.py:107-116): out[0] = mean (a - b)^2 over count elements with element strides
+ * a->sv, b->sv (sn, sc unused); sum: one double of scratch. */
+int dycon_sym_mse_fwd(const dycon_view_t* a, const dycon_view_t* b, long long count, double* sum, float* out, dycon_stream_t stream);
+/* grad = g_up[0] * d out / d a (pass (b, a) for the second argument) */
+int dycon_sym_mse_bwd(const dycon_view_t* a, const dycon_view_t* b, long long count, const float* g_up, const dycon_view_t* grad,
+                      dycon_stream_t stream);
+/* losses.compute_kl_loss(a, b) (utils/losses.py:208-219): (kl_div(log_softmax(a,-1), softmax(b,-1), 'none').mean() + the same with a
+ * and b exchanged) / 2, softmax over the LAST dimension: the views address n C V rows, row (in, ic, iv) at p + in sn + ic sc + iv sv,
+ * of L elements with element stride sla / slb.  1 <= L <= 1024.  sum: one double of scratch. */
+int dycon_kl_rows_fwd(const dycon_view_t* a, long long sla, const dycon_view_t* b, long long slb, long long n, long long C,
+                      long long V, int L, double* sum, float* out, dycon_stream_t stream);
+/* grad = g_up[0] * d out / d a (the loss is symmetric: pass (b, a) for the second argument); grad rows as the inputs', stride slg */
+int dycon_kl_rows_bwd(const dycon_view_t* a, long long sla, const dycon_view_t* b, long long slb, long long n, long long C,
+                      long long V, int L, const float* g_up, const dycon_view_t* grad, long long slg, dycon_stream_t stream);
+/* losses.FocalLoss(gamma, alpha, size_average)(x, target) (utils/losses.py:119-153): out[0] = mean or sum over the n V voxels of
+ * -(1 - pt)^gamma alpha[t] log pt, pt = softmax(x, 1)[t], t = target[n V + v] (contiguous; target_kind 1: uint8, 2: int64).
+ * alpha_host: C host floats or NULL (= 1).  sum: one double of scratch. */
+int dycon_focal_fwd(const dycon_view_t* x, const void* target, int target_kind, long long n, int C, long long V, float gamma,
+                    const float* alpha_host, int size_average, double* sum, float* out, dycon_stream_t stream);
+/* grad = g_up[0] * d out / d x with pt held constant, as the reference detaches it (utils/losses.py:141) */
+int dycon_focal_bwd(const dycon_view_t* x, const void* target, int target_kind, long long n, int C, long long V, float gamma,
+                    const float* alpha_host, int size_average, const float* g_up, const dycon_view_t* grad, dycon_stream_t stream);
+
 /* rows of (R, C): y = x / max(||x||, eps)   (F.normalize, train_DyCON_BraTS19.py:316-323) */
 int dycon_l2norm_fwd(const void* x, void* y, float* norms, int dtype, long long R, int C, float eps,
                      dycon_stream_t stream);

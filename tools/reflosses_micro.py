@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Forward + backward time of the reference's remaining loss callables (utils/losses.py second half, csrc/reflosses.hip) at the
+training shape (4, 2, 96, 96, 96), next to the torch composition of the same formula on the same GPU in the same process.
+
+HIP events around forward + backward, warm-up, then the median of the timed repeats.  GB/s is the kernels' ALGORITHMIC traffic (each
+input read once per kernel that needs it, each output written once) over the HIP time; the torch column moves several times that.
+The legacy losses.FeCLoss runs the fecl kernels, which tools/fecl_micro.py measures.
+
+    python tools/reflosses_micro.py --out profiles/reflosses_micro.txt --commit $(git rev-parse --short HEAD)
+"""
+import argparse
+import datetime
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from dycon_paper_replication_amd.utils import losses  # noqa: E402
+from test_losses_extra_cpu import R, calls, run_call  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0      # MI355X data sheet
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return statistics.median(ms), min(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--commit", default="unknown")
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    dev = "cuda:0"
+    gen = torch.Generator().manual_seed(3)
+    shape = (4, 2, 96, 96, 96)
+    x = (2 * torch.randn(*shape, generator=gen)).to(dev)
+    y = x + (1.5 * torch.randn(*shape, generator=gen)).to(dev)
+    label = torch.randint(0, 2, (4, 96, 96, 96), generator=gen).to(dev)
+    t = {"a": x, "b": y, "p": torch.softmax(x, 1), "q": torch.softmax(y, 1), "label": label, "tf": (label == 1).float(),
+         "r": (0.5 + torch.rand(4, 1, 96, 96, 96, generator=gen)).to(dev), "C": 2}
+    T = x.numel() * 4 / 1e9          # GB of one (4, 2, 96^3) fp32 tensor; a class slice, a map or the int64 labels are T/2, T/2, T
+    # algorithmic GB of forward + backward (all differentiable inputs)
+    traffic = {"dice1": 2 * T, "dice1_soft": 3 * T, "softmax_dice": 8 * T, "entropy_min": 3 * T, "entropy_map": 4 * T,
+               "entropy_loss": 3 * T, "entropy_loss_map": 4 * T, "sym_mse": 8 * T, "compute_kl": 8 * T, "focal0": 5 * T}
+    lines = [f"# reflosses_micro  {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}  commit {a.commit}",
+             f"# {torch.cuda.get_device_name(0)}, torch {torch.__version__}; shape {shape} fp32, forward + backward, "
+             f"median of {a.reps} after {a.warmup} warm-up (min in brackets)",
+             f"# GB/s: algorithmic bytes of the HIP kernels / HIP median; % of {HBM_PEAK_GBS:.0f} GB/s HBM peak",
+             f"{'callable':<18}{'HIP ms':>16}{'torch ms':>18}{'speed-up':>10}{'alg. GB':>9}{'GB/s':>8}{'% peak':>8}"]
+    tab = calls(2)
+    for name, gb in traffic.items():
+        fn, wrt = tab[name]
+        hip_ms, hip_min = timed(lambda: run_call(losses, fn, wrt, t), a.warmup, a.reps)
+        th_ms, th_min = timed(lambda: run_call(R, fn, wrt, t), a.warmup, a.reps)
+        gbs = gb / (hip_ms * 1e-3)
+        lines.append(f"{name:<18}{hip_ms:>8.3f} ({hip_min:.3f}){th_ms:>9.3f} ({th_min:.3f}){th_ms / hip_ms:>9.1f}x{gb:>9.3f}{gbs:>8.0f}"
+                     f"{100 * gbs / HBM_PEAK_GBS:>7.1f}%")
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()
