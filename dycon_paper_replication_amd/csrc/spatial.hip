@@ -20,7 +20,9 @@ struct Philox {
         return make_uint4(c0, c1, c2, c3);
     }
 };
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
+// (0, 1]: x >> 8 = 2^24 - 1 gives 16777215.5f, which rounds to 2^24, i.e. exactly 1.0.  Harmless: log(1) = 0 in Box-Muller, and
+// 1 > p keeps the element (p < 1).  The lower end is 2^-25, never 0.
+__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // ------------------------------------------------------------------------------------------------
 // MaxPool3d(2): first maximum in (dz,dy,dx) scan order wins (ATen CPU/CUDA tie rule; matters because
