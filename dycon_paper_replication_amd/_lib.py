@@ -64,6 +64,7 @@ SIGNATURES = {
     "dycon_maxpool2_bwd": (I, [P, P, P, I, I, I, I, I, I, P]),
     "dycon_trilinear_fwd": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "dycon_trilinear_bwd": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dycon_upconv_k3": (I, [P, P, P, P, I, I, I, I, I, I, I, P]),
     "dycon_copy_channels": (I, [P, I, I, P, I, I, L, I, I, P]),
     "dycon_relu_fwd": (I, [P, P, P, P, I, I, L, I, P]),
     "dycon_relu_bwd": (I, [P, P, P, P, I, I, L, I, P]),

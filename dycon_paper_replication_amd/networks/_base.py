@@ -157,11 +157,18 @@ class HipSegNet(nn.Module):
         self._drop_calls += 1
         return DropoutSpec("philox", seed=self._drop_seed, offset=self._drop_calls * (1 << 24))
 
-    def forward(self, x):
+    def forward(self, x, turnoff_drop=False):
+        """turnoff_drop: dropout is off for this call (VNet.py:231-239); the default issues the launches it always issued"""
         if not x.is_cuda:
             raise RuntimeError("HipSegNet runs on the MI355X only (no CPU fallback): move the module and input to 'cuda'")
         if x.dim() != 5 or x.shape[1] != self.in_channels:
             raise ValueError(f"expected (B,{self.in_channels},D,H,W), got {tuple(x.shape)}")
         if any(s % 16 for s in x.shape[2:]):
             raise ValueError("D, H, W must be divisible by 16")
-        return _NetFunction.apply(x.float().contiguous(), self, *self.parameters())
+        if not turnoff_drop:
+            return _NetFunction.apply(x.float().contiguous(), self, *self.parameters())
+        has_dropout, self.has_dropout = self.has_dropout, False
+        try:
+            return _NetFunction.apply(x.float().contiguous(), self, *self.parameters())
+        finally:
+            self.has_dropout = has_dropout

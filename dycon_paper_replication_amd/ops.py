@@ -581,6 +581,19 @@ def trilinear_bwd(gy, in_shape, align_corners, coff=0):
     return gx
 
 
+def upconv_k3(x, wfrag, bias, Cout, out=None):
+    """Conv3d(k=3, padding=1) of the trilinear x2 (align_corners=False) up-sampling of x, in one kernel (VNet.py:121-142):
+    x (B, D, H, W, Cin) -> (B, 2D, 2H, 2W, Cout).  wfrag: pack_bfrag(w, dtype, 27, Cin, Cout, Cout, 1, 27, 0, Cin * 27), the
+    operand conv_gemm takes.  The up-sampled tensor is never written: the region counts the low-resolution read, the output
+    write and the weights."""
+    B, D, H, W, Cin = x.shape
+    if out is None:
+        out = torch.empty((B, 2 * D, 2 * H, 2 * W, Cout), dtype=x.dtype, device=x.device)
+    with _Region("upconv_k3", (x.numel() + out.numel()) * _es(x) + 27 * Cin * Cout * _es(x), 2 * (out.numel() // Cout) * 27 * Cin * Cout):
+        call("dycon_upconv_k3", _p(x), _p(wfrag), _p(bias), _p(out), dt(x), B, D, H, W, Cin, Cout, _s())
+    return out
+
+
 def copy_channels(src, soff, dst, doff, C):
     rows = src.numel() // src.shape[-1]
     call("dycon_copy_channels", _p(src), src.shape[-1], soff, _p(dst), dst.shape[-1], doff, rows, C, dt(src), _s())

@@ -250,6 +250,15 @@ int dycon_trilinear_fwd(const void* x, void* y, int dtype, int B, int Di, int Hi
 int dycon_trilinear_bwd(const void* gy, void* gx, int dtype, int B, int Di, int Hi, int Wi, int Do,
                         int Ho, int Wo, int C, int ldy, int coff, int align_corners,
                         dycon_stream_t stream);
+/* Upsampling block's operator (networks/VNet.py:121-142): nn.Upsample(scale_factor=2, mode='trilinear', align_corners=False)
+ * followed by nn.Conv3d(Cin, Cout, 3, padding=1), as ONE kernel:
+ *   y = conv_k3_pad1(upsample_x2(x)) + bias,   x (B, Di, Hi, Wi, Cin) -> y (B, 2Di, 2Hi, 2Wi, Cout), NDHWC, fp32 or bf16 storage,
+ * fp32 accumulation.  The zero padding of the convolution applies on the up-sampled grid; the up-sampled tensor is formed tile
+ * by tile in LDS and never written to memory (csrc/upconv.hip).  wfrag: dycon_pack_bfrag(T = 27, Cin, N = Cout) of the Conv3d
+ * weight, as for dycon_conv_gemm (k = tap * Cin + c).  bias may be NULL.
+ * Channels: Cin 16, 48 or a multiple of 32; Cout a multiple of 16; anything else is DYCON_ERR_INVALID.  No workspace. */
+int dycon_upconv_k3(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int B,
+                    int Di, int Hi, int Wi, int Cin, int Cout, dycon_stream_t stream);
 /* dst[row, doff + c] = src[row, soff + c]  (concat / split of channel slices) */
 int dycon_copy_channels(const void* src, int lds, int soff, void* dst, int ldd, int doff,
                         long long rows, int C, int dtype, dycon_stream_t stream);
