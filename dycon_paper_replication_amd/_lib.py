@@ -197,11 +197,8 @@ RECORDER = None
 # (producer and consumer kernels on the same GPU; the one host-read value of a step, the NaN flag, keeps torch's event): their
 # events are created here without that fence and recorded / waited through ctypes (also cheaper on the host than the torch objects).
 # Measured (profiles/r03_ablation_timing.txt): step 5.05 ms with torch's flags, 4.95 ms with hipEventDisableSystemFence, 5.05 ms with
-# hipEventReleaseToDevice (the release flags are mutually exclusive).  DYCON_EVENT_FLAGS = default | nofence | device (diagnostic).
-HIP_EVENT_DISABLE_TIMING, HIP_EVENT_NO_SYSTEM_FENCE, HIP_EVENT_RELEASE_TO_DEVICE = 0x2, 0x20000000, 0x40000000
-_EVENT_FLAGS = {"default": HIP_EVENT_DISABLE_TIMING, "nofence": HIP_EVENT_DISABLE_TIMING | HIP_EVENT_NO_SYSTEM_FENCE,
-                "device": HIP_EVENT_DISABLE_TIMING | HIP_EVENT_RELEASE_TO_DEVICE}
-EVENT_MODE = os.environ.get("DYCON_EVENT_FLAGS", "nofence")
+# hipEventReleaseToDevice (0x40000000; the release flags are mutually exclusive).
+HIP_EVENT_DISABLE_TIMING, HIP_EVENT_NO_SYSTEM_FENCE = 0x2, 0x20000000
 _hip = None
 
 
@@ -224,7 +221,7 @@ class HipEvent:
 
     def __init__(self):
         ev = P()
-        rc = hip().hipEventCreateWithFlags(C.byref(ev), _EVENT_FLAGS[EVENT_MODE])
+        rc = hip().hipEventCreateWithFlags(C.byref(ev), HIP_EVENT_DISABLE_TIMING | HIP_EVENT_NO_SYSTEM_FENCE)
         if rc:
             raise DyconLibraryError(f"hipEventCreateWithFlags failed ({rc})")
         self.h = ev.value

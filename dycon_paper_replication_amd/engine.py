@@ -11,7 +11,6 @@ always fp32.  Parameters stay in the reference's torch layouts/names (state_dict
 """
 from __future__ import annotations
 
-import os
 from collections import OrderedDict
 from typing import Dict, Optional
 
@@ -22,10 +21,6 @@ from ._lib import CONV_1X1, CONV_K2S2, CONV_K3
 
 UNET_FILTERS = (16, 32, 64, 128, 256)
 VNET_NORMS = ("groupnorm", "instancenorm", "batchnorm", "none")      # VNet.py:17-24
-# tools/ablate.py only (timing experiments with parts of the step switched off, each case in a fresh process): read ONCE at import,
-# immutable afterwards -- nothing in a training or test process can switch a part of the step off
-ABLATE = frozenset(a for a in os.environ.get("DYCON_ABLATE", "").split(",") if a)
-ABLATE_N = int(os.environ.get("DYCON_ABLATE_N", "0"))
 
 
 # --------------------------------------------------------------------------------------
@@ -211,21 +206,9 @@ class Engine:
         self.on_param_grads = None   # optional callback(name): called in backward once a layer's parameter gradients are enqueued
         self.wgrad_stream = None     # optional side stream for the weight-gradient launches of the backward (set by the trainer)
         self.wgrad_stream2 = None    # optional second one: the convolutions' weight gradients then alternate between the two
-        self.wgrad_stream3 = None    # (diagnostic) a third
         self._wg_flip = 0
         self.feat_stream = None      # optional stream for the feature branch (projection head forward + backward), see forward()
         self.mark = None             # optional callback(tag, stream): timeline marks (trainer._mark)
-        self.stage_hook = None       # optional callback(name): called in the V-Net forward when the encoder tensor `name` (x1..x5) is enqueued
-        # per-step arena of zeroed doubles for the accumulator form of the norms (ops.norm_fwd / norm_bwd `acc`): slices are handed
-        # out in call order; whoever owns the arena clears it once per step BEFORE the first norm (the trainer: one launch for both
-        # nets; a stand-alone engine: at the start of forward()).
-        # Measured SLOWER than partials -> finalize -> apply (5.8 -> 6.4 ms/step with one accumulator copy per sample: <= 512 adds
-        # per address; 6.6 ms with 32 copies: the prologue of every apply workgroup then reads 64 doubles per channel) -- DESIGN.md
-        # section 9.  Kept (tested: test_norm_accumulator_form_equals_three_launch_form), off by default.
-        self.use_acc = False
-        self.acc_arena = None
-        self.acc_external = False
-        self._acc_off = 0
         self.Gs = {}
         self._head_range = (0, 0)
         self._wws = {}               # per-layer workspaces of the weight-gradient launches
@@ -233,13 +216,10 @@ class Engine:
         # less, but measured SLOWER (5.8 -> 6.1 ms/step): the norm's workgroups own 8-16 channels of one sample, so they read the
         # fp32 slabs in 32-byte pieces at a C*4-byte stride where splitk_finish streams them fully coalesced.  Off by default.
         self.fuse_finish = False
-        self.fuse_head = True            # V-Net: the 2-class head inside the last normalisation's passes (_norm_head)
         self.conv_stats = False          # 48^3 level: the persistent convolution takes the statistics of its output (ops.conv_gemm_stats);
                                          # measured neutral for the step (+5 us per convolution against a 7 us statistics launch): off
-        self.conv_stats96 = False        # 96^3 level (conv_k3_c1 / conv_k3_p16): the same; measured neutral as well (TrainConfig.conv_stats96)
+        self.conv_stats96 = False        # 96^3 level (conv_k3_c1 / conv_k3_p16): the same; measured neutral as well
         self._stat_parts = {}
-        self.fuse_first = True           # V-Net: block_one's norm backward formed on load by the first layer's weight gradient (_first_block)
-        self.one_pass_first = True       # ... as ONE pass (dycon_first_block_bwd) instead of statistics + weight gradient
         self._deferred = {}
         self._pending_dparams = []
         self.tape = []
@@ -399,13 +379,21 @@ class Engine:
         out_dtype = out_dtype or dtype
         first_lds = (kind == "k3" and Cin == 1 and dtype == torch.bfloat16 and Cout in (16, 32, 64) and out_dtype == dtype
                      and x.shape[1] * x.shape[2] * x.shape[3] >= 13824)
+
+        def conv_with_stats(wf, want):
+            """the persistent kernel also takes the statistics of its output (the norm that follows skips its statistics pass);
+            None where that is not wanted or the library does not serve the shape"""
+            chunks = ops.conv_stats_chunks(x, Cin, Cout) if (norm_groups and want) else 0
+            if not chunks:
+                return None
+            y, part = ops.conv_gemm_stats(x, wf, b, Cout, chunks)
+            self._stat_parts[id(y)] = (part, chunks)
+            return y
+
         if first_lds:   # first layer on the matrix cores: K = 27 taps in one 32-wide k-step (conv_k3_c1_kernel), see dycon_hip.h
             wf = self._pk((name, "f1"), "frag", w, 27, 1, Cout, Cout, 1, 27, 0, 27)
-            chunks = ops.conv_stats_chunks(x, Cin, Cout) if (norm_groups and self.conv_stats96 and Cout == 16) else 0
-            if chunks:      # the persistent kernel also takes the statistics of its output (see below)
-                y, part = ops.conv_gemm_stats(x, wf, b, Cout, chunks)
-                self._stat_parts[id(y)] = (part, chunks)
-            else:
+            y = conv_with_stats(wf, self.conv_stats96 and Cout == 16)
+            if y is None:
                 y = ops.conv_gemm(x, wf, b, CONV_K3, Cout, Cout)
         elif skinny:
             assert kind in ("k3", "1x1"), "skinny path only for the first conv and the 1x1 heads"
@@ -422,17 +410,13 @@ class Engine:
             # a GroupNorm / InstanceNorm of the one-launch kind follows (norm_groups > 0): leave a split-K finish to it
             Vo = (x.shape[1] * x.shape[2] * x.shape[3]) // (8 if kind == "k2s2" else 1)
             want_stats = self.conv_stats96 if (Cin, Cout) == (16, 16) else self.conv_stats       # 96^3 level / 48^3 level
-            chunks = (ops.conv_stats_chunks(x, Cin, Cout)
-                      if (norm_groups and want_stats and kind == "k3" and out_dtype == dtype and dtype == torch.bfloat16) else 0)
-            if chunks:      # the persistent kernel also takes the statistics of its output: the norm that follows skips its statistics pass
-                y, part = ops.conv_gemm_stats(x, wf, b, Cout, chunks)
-                self._stat_parts[id(y)] = (part, chunks)
-            elif (norm_groups and self.fuse_finish and dtype == torch.bfloat16 and out_dtype == dtype
-                    and ops.norm_fwd_is_fused(x, Vo, Cout, norm_groups)):
+            y = conv_with_stats(wf, want_stats and kind == "k3" and out_dtype == dtype and dtype == torch.bfloat16)
+            if y is None and (norm_groups and self.fuse_finish and dtype == torch.bfloat16 and out_dtype == dtype
+                              and ops.norm_fwd_is_fused(x, Vo, Cout, norm_groups)):
                 y, dc = ops.conv_gemm(x, wf, b, mode, Cout, Cout, defer_finish=True)
                 if dc is not None:
                     self._deferred[id(y)] = dc
-            else:
+            elif y is None:
                 y = ops.conv_gemm(x, wf, b, mode, Cout, Cout)
 
         if self.recording:
@@ -457,22 +441,14 @@ class Engine:
 
             def bwd():
                 gy = self._take(y)
-                if "wgrad" in ABLATE:
-                    pass
-                elif "wgrad_events_only" in ABLATE and self.wgrad_stream is not None:      # the fork, without the kernels
-                    ops.fork(ops.cur_stream(), self.wgrad_stream)
-                elif "wgrad_no_events" in ABLATE and self.wgrad_stream is not None:        # the kernels, without the fork (a race: timing only)
-                    with ops.on_stream(self.wgrad_stream, light=True):
-                        wgrad(gy)
-                elif self.wgrad_stream is not None:
+                if self.wgrad_stream is not None:
                     # The weight gradient only feeds the optimiser; the data gradient is the critical chain.  Enqueue the former on a
                     # second HIP stream (behind an event that marks gy ready) so the small-level wgrad / reduce launches fill the
                     # CUs the latency-bound dgrad / norm-backward kernels leave idle.  backward() joins the streams at the end.
                     wst = self.wgrad_stream
                     if self.wgrad_stream2 is not None:
-                        ring = [self.wgrad_stream, self.wgrad_stream2] + ([self.wgrad_stream3] if self.wgrad_stream3 is not None else [])
-                        self._wg_flip = (self._wg_flip + 1) % len(ring)
-                        wst = ring[self._wg_flip]
+                        self._wg_flip = (self._wg_flip + 1) % 2       # advanced BEFORE use
+                        wst = (self.wgrad_stream, self.wgrad_stream2)[self._wg_flip]
                     ops.fork(ops.cur_stream(), wst)
                     with ops.on_stream(wst, light=True):
                         self._flush_dparams()
@@ -483,9 +459,6 @@ class Engine:
                 if not need_gx:
                     return
                 cur = self._peek(x)
-                if "dgrad" in ABLATE:
-                    self._put(x, cur if cur is not None else torch.empty_like(x))
-                    return
                 if skinny:             # 1x1 head: gx[m,ci] = sum_co gy[m,co] W[co][ci]
                     wd = self._pk((name, "tcn_d"), "tcn", w, 1, Cout, Cin, Cin, 0, Cin, 0, 1)
                     gx = ops.conv_direct(gy, wd, None, CONV_1X1, Cin, x.dtype, out=cur, accumulate=cur is not None)
@@ -508,16 +481,6 @@ class Engine:
             self.tape.append(bwd)
         return y
 
-    ACC_DOUBLES = 1 << 20      # 8 MB: ~40 slices of Nb x 32 slots x C x 2 doubles
-
-    def _acc(self, n):
-        """n zeroed doubles of this step's arena (None when the arena is exhausted: the caller then takes the three-launch path)"""
-        if not self.use_acc or self.acc_arena is None or self._acc_off + n > self.acc_arena.numel():
-            return None
-        a = self.acc_arena[self._acc_off:self._acc_off + n]
-        self._acc_off += n
-        return a
-
     def _flush_dparams(self):
         """deferred dgamma / dbeta sums of the norms whose backward has been enqueued (call inside the weight-gradient section)"""
         for pend in self._pending_dparams:
@@ -526,11 +489,32 @@ class Engine:
         self._pending_dparams = []
 
     # ---------------------------------------------------------------- norm (+ReLU, +skip)
-    def _norm(self, prefix, z, kind, relu=True, skip=None, training=True, chan_scale=None):
+    def _norm_site(self, prefix, z, kind):
+        """The norm module `prefix` over the NDHWC tensor z as the kernels take it: (Nb samples of V voxels, C channels in G groups,
+        gamma, beta, running mean, running variance).  BatchNorm is ONE sample of B*V voxels with a group per channel."""
         B, C = z.shape[0], z.shape[-1]
         V = z.numel() // (B * C)
-        gamma = beta = None
-        rm = rv = None
+        if kind == "in":               # InstanceNorm3d: affine=False
+            return B, V, C, C, None, None, None, None
+        if kind not in ("gn", "bn"):
+            raise ValueError(kind)
+        gamma, beta = self.p[prefix + ".weight"], self.p[prefix + ".bias"]
+        if kind == "gn":
+            return B, V, C, 16, gamma, beta, None, None
+        return 1, B * V, C, C, gamma, beta, self.buf.get(prefix + ".running_mean"), self.buf.get(prefix + ".running_var")
+
+    @staticmethod
+    def _eval_stats(rm, rv):
+        """(mean, rstd) pairs of an eval-mode BatchNorm from its running statistics"""
+        return torch.stack([rm, torch.rsqrt(rv + 1e-5)], 1).reshape(-1).contiguous()
+
+    def _count_batch(self, prefix):
+        """num_batches_tracked += 1 of the BatchNorm `prefix` (where the module has the buffer)"""
+        nbt = self.buf.get(prefix + ".num_batches_tracked")
+        if nbt is not None:
+            ops.rec(lambda: nbt.add_(1))
+
+    def _norm(self, prefix, z, kind, relu=True, skip=None, training=True, chan_scale=None):
         if kind == "bn" and chan_scale is not None:
             # BatchNorm runs as ONE sample of B*V voxels, while nn.Dropout3d draws a mask per (sample, channel) (VNet.py:195-196,
             # 225-226): the norm kernels index their dropout factor per norm-sample, so here the factor is applied by its own pass
@@ -541,16 +525,7 @@ class Engine:
                     self._give(y, ops.scale_channels(self._take(y2), chan_scale))
                 self.tape.append(bwd_scale)
             return y2
-        if kind == "gn":
-            Nb, G = B, 16
-            gamma, beta = self.p[prefix + ".weight"], self.p[prefix + ".bias"]
-        elif kind == "in":
-            Nb, G = B, C
-        elif kind == "bn":
-            Nb, G, V = 1, C, B * V
-            gamma, beta = self.p[prefix + ".weight"], self.p[prefix + ".bias"]
-            rm, rv = self.buf.get(prefix + ".running_mean"), self.buf.get(prefix + ".running_var")
-        elif kind == "none":           # normalization='none': conv -> ReLU (VNet.py:23-24); same fusions (dropout factor, skip add)
+        if kind == "none":             # normalization='none': conv -> ReLU (VNet.py:23-24); same fusions (dropout factor, skip add)
             assert relu
             y = ops.relu_fwd(z, skip, chan_scale)
             if self.recording:
@@ -561,13 +536,12 @@ class Engine:
                     self._give(z, ops.relu_bwd(z, gy, chan_scale))
                 self.tape.append(bwd_relu)
             return y
-        else:
-            raise ValueError(kind)
+        Nb, V, C, G, gamma, beta, rm, rv = self._norm_site(prefix, z, kind)
         # z is kept: the ReLU is not invertible, so the backward needs the pre-norm tensor (xhat of the
         # clamped voxels still enters the group means)
         if kind == "bn" and not training:
             # eval-mode BatchNorm (ISLES teacher, train_DyCON_ISLES22.py:114): running statistics
-            stats = torch.stack([rm, torch.rsqrt(rv + 1e-5)], 1).reshape(-1).contiguous()
+            stats = self._eval_stats(rm, rv)
             y = ops.norm_apply(z, stats, Nb, V, C, G, gamma, beta, relu, skip, chan_scale=chan_scale)
         elif id(z) in self._stat_parts and kind in ("gn", "in"):     # the producing convolution left the statistics partials behind
             part, chunks = self._stat_parts.pop(id(z))
@@ -576,12 +550,10 @@ class Engine:
             y, stats = ops.norm_fwd_slab(z, self._deferred.pop(id(z)), Nb, V, C, G, gamma, beta, relu, skip, chan_scale)
         else:
             upd = kind == "bn" and training and self.update_bn
-            acc = None if ops.norm_fwd_is_fused(z, V, C, G) else self._acc(ops.query("dycon_norm_acc_doubles", Nb, V, C))
             y, stats = ops.norm_fwd(z, Nb, V, C, G, gamma, beta, relu, skip, chan_scale, 1e-5, rm if upd else None,
-                                    rv if upd else None, 0.1, acc=acc)
-            if upd and prefix + ".num_batches_tracked" in self.buf:
-                nbt = self.buf[prefix + ".num_batches_tracked"]
-                ops.rec(lambda: nbt.add_(1))
+                                    rv if upd else None, 0.1)
+            if upd:
+                self._count_batch(prefix)
         if self.recording:
             def bwd():
                 gy = self._take(y)
@@ -589,18 +561,15 @@ class Engine:
                     self._give(skip, gy)
                 dg = self.g[prefix + ".weight"] if gamma is not None else None
                 db = self.g[prefix + ".bias"] if beta is not None else None
-                acc = None if ops.norm_fwd_is_fused(z, V, C, G) else self._acc(ops.query("dycon_norm_acc_doubles", Nb, V, C))
-                if "norm_bwd" in ABLATE:
-                    gz = gy
-                elif acc is None and self.wgrad_stream is not None and dg is not None:
-                    # one-launch shapes: the tiny sum of the per-sample dgamma / dbeta contributions leaves the dependent chain -- it
+                if self.wgrad_stream is not None and dg is not None:
+                    # the tiny sum of the per-sample dgamma / dbeta contributions leaves the dependent chain -- it
                     # is enqueued on the weight-gradient stream by the convolution's backward that follows (same fork event)
                     gz, pend = ops.norm_bwd(z, False, gy, stats, Nb, V, C, G, gamma, beta, relu, dg, db, chan_scale=chan_scale,
                                             defer_dparams=True)
                     if pend is not None:
                         self._pending_dparams.append(pend)
                 else:
-                    gz = ops.norm_bwd(z, False, gy, stats, Nb, V, C, G, gamma, beta, relu, dg, db, chan_scale=chan_scale, acc=acc)
+                    gz = ops.norm_bwd(z, False, gy, stats, Nb, V, C, G, gamma, beta, relu, dg, db, chan_scale=chan_scale)
                 if self.on_param_grads is not None and gamma is not None:
                     self.on_param_grads(prefix + ".weight")
                 self._give(z, gz)
@@ -609,8 +578,8 @@ class Engine:
 
     def _first_block(self, name, x, kind, training):
         """block_one (conv 1 -> 16, norm, ReLU; VNet.py:176): the normalisation's data gradient has ONE consumer, the convolution's weight
-        gradient (the image needs no gradient), so the backward never stores it: norm statistics pass + finalize on the chain, then the
-        weight gradient forms it on load (csrc/conv.hip, wgrad_k3_c1_kernel<true>) -- the backward-apply pass over the step's largest
+        gradient (the image needs no gradient), so the backward never stores it: ONE pass over (x, z, gy) takes the
+        sums that dW, db, dgamma and dbeta are made of (dycon_first_block_bwd) -- the backward-apply pass over the step's largest
         tensor and the weight gradient's read of its result are gone from the exposed tail of the backward."""
         cname, nname = f"{name}.conv.0", f"{name}.conv.1"
         rec, self.recording = self.recording, False
@@ -618,18 +587,7 @@ class Engine:
             z = self._conv(cname, x, "k3", need_gx=False, norm_groups=(16 if kind == "gn" else (16 if kind == "in" else 0)))
         finally:
             self.recording = rec
-        B, C = z.shape[0], z.shape[-1]
-        V = z.numel() // (B * C)
-        gamma = beta = rm = rv = None
-        if kind == "gn":
-            Nb, G = B, 16
-            gamma, beta = self.p[nname + ".weight"], self.p[nname + ".bias"]
-        elif kind == "in":
-            Nb, G = B, C
-        else:
-            Nb, G, V = 1, C, B * V
-            gamma, beta = self.p[nname + ".weight"], self.p[nname + ".bias"]
-            rm, rv = self.buf.get(nname + ".running_mean"), self.buf.get(nname + ".running_var")
+        Nb, V, C, G, gamma, beta, rm, rv = self._norm_site(nname, z, kind)
         upd = kind == "bn" and training and self.update_bn
         if id(z) in self._stat_parts and kind in ("gn", "in"):     # the convolution left the statistics partials behind
             part, chunks = self._stat_parts.pop(id(z))
@@ -637,34 +595,19 @@ class Engine:
         else:
             self._stat_parts.pop(id(z), None)
             y, stats = ops.norm_fwd(z, Nb, V, C, G, gamma, beta, True, None, None, 1e-5, rm if upd else None, rv if upd else None, 0.1)
-        if upd and nname + ".num_batches_tracked" in self.buf:
-            nbt = self.buf[nname + ".num_batches_tracked"]
-            ops.rec(lambda: nbt.add_(1))
+        if upd:
+            self._count_batch(nname)
         if rec:
             def bwd():
                 gy = self._take(y)
                 dg = self.g[nname + ".weight"] if gamma is not None else None
                 db = self.g[nname + ".bias"] if beta is not None else None
                 gw, gb = self.g[cname + ".weight"], self.g[cname + ".bias"]
-                if self.one_pass_first:       # everything in ONE pass over (x, z, gy), on the chain (it is the exposed tail of the backward)
-                    wws = self._wws.get((cname, "#fb", tuple(x.shape[:4])))
-                    if wws is None:
-                        wws = self._wws[(cname, "#fb", tuple(x.shape[:4]))] = ops._ws(ops.query("dycon_first_block_bwd_workspace", *x.shape[:4]), x)
-                    ops.first_block_bwd(x, z, gy, stats, Nb, G, gw, gb, gamma, beta, True, dg, db, None, ws=wws)
-                else:
-                    nws, ab = ops.norm_bwd_stats(z, gy, stats, Nb, V, C, G, gamma, beta, True, dg, db)
-                    wws = self._wws.get((cname, "#nb", tuple(x.shape[:4])))
-                    if wws is None:
-                        wws = self._wws[(cname, "#nb", tuple(x.shape[:4]))] = ops._ws(ops.query("dycon_conv1_wgrad_normbwd_workspace", *x.shape[:4]), x)
-                    if self.wgrad_stream is not None:
-                        ops.fork(ops.cur_stream(), self.wgrad_stream)
-                        with ops.on_stream(self.wgrad_stream, light=True):
-                            self._flush_dparams()
-                            ops.conv1_wgrad_normbwd(x, z, gy, stats, ab, Nb, G, gw, gb, gamma, beta, True, None, ws=wws)
-                        for t in (gy, nws):
-                            t.record_stream(self.wgrad_stream)
-                    else:
-                        ops.conv1_wgrad_normbwd(x, z, gy, stats, ab, Nb, G, gw, gb, gamma, beta, True, None, ws=wws)
+                # everything in ONE pass over (x, z, gy), on the chain (it is the exposed tail of the backward)
+                wws = self._wws.get((cname, "#fb", tuple(x.shape[:4])))
+                if wws is None:
+                    wws = self._wws[(cname, "#fb", tuple(x.shape[:4]))] = ops._ws(ops.query("dycon_first_block_bwd_workspace", *x.shape[:4]), x)
+                ops.first_block_bwd(x, z, gy, stats, Nb, G, gw, gb, gamma, beta, True, dg, db, None, ws=wws)
                 if self.on_param_grads is not None:
                     if gamma is not None:
                         self.on_param_grads(nname + ".weight")
@@ -676,22 +619,11 @@ class Engine:
         """block_nine's norm -> ReLU [-> Dropout3d] -> out_conv (VNet.py:225-227) as ONE pass over the pre-norm tensor, forward and
         backward: the normalised 16-channel tensor (the largest activation of the step) and its gradient are never written
         (csrc/norm.hip, dycon_norm_head_*).  Same logits as _norm + _conv('1x1') bit for bit, same data gradient to fp32 round-off."""
-        B, C = z.shape[0], z.shape[-1]
-        V = z.numel() // (B * C)
-        gamma = beta = rm = rv = None
-        if kind == "gn":
-            Nb, G = B, 16
-            gamma, beta = self.p[prefix + ".weight"], self.p[prefix + ".bias"]
-        elif kind == "in":
-            Nb, G = B, C
-        else:
-            Nb, G, V = 1, C, B * V
-            gamma, beta = self.p[prefix + ".weight"], self.p[prefix + ".bias"]
-            rm, rv = self.buf.get(prefix + ".running_mean"), self.buf.get(prefix + ".running_var")
+        Nb, V, C, G, gamma, beta, rm, rv = self._norm_site(prefix, z, kind)
         hw, hb = self.p[head + ".weight"], self.p[head + ".bias"]
         if kind == "bn" and not training:
             self._stat_parts.pop(id(z), None)
-            stats = torch.stack([rm, torch.rsqrt(rv + 1e-5)], 1).reshape(-1).contiguous()
+            stats = self._eval_stats(rm, rv)
         elif id(z) in self._stat_parts and kind in ("gn", "in"):   # block_nine's convolution left the statistics partials behind
             part, chunks = self._stat_parts.pop(id(z))
             stats = ops.norm_stats_parts(z, part, chunks, Nb, V, C, G)
@@ -699,9 +631,8 @@ class Engine:
             self._stat_parts.pop(id(z), None)
             upd = kind == "bn" and training and self.update_bn
             stats = ops.norm_stats(z, Nb, V, C, G, 1e-5, rm if upd else None, rv if upd else None, 0.1)
-            if upd and prefix + ".num_batches_tracked" in self.buf:
-                nbt = self.buf[prefix + ".num_batches_tracked"]
-                ops.rec(lambda: nbt.add_(1))
+            if upd:
+                self._count_batch(prefix)
         logits = ops.norm_head_fwd(z, stats, Nb, V, G, hw, hb, gamma, beta, True, chan_scale)
         if self.recording:
             def bwd():
@@ -830,11 +761,9 @@ class Engine:
             if upd and "scatter_stats" in t:
                 ops.copy_segments(t["scatter_stats"])
                 for j in range(1, 5):
-                    nbt = self.buf.get(f"aspp.aspp{j}.bn.num_batches_tracked")
-                    if nbt is not None:
-                        ops.rec(lambda nbt=nbt: nbt.add_(1))
+                    self._count_batch(f"aspp.aspp{j}.bn")
         else:
-            st = torch.stack([rm, torch.rsqrt(rv + 1e-5)], 1).reshape(-1).contiguous()
+            st = self._eval_stats(rm, rv)
             ybr = ops.norm_apply(z, st, 1, M, N, N, gam, bet, True)
         # -- pool branch (B, c): mean -> 1x1 -> [BN if B > 1] -> ReLU, then its share of conv1 as a per-sample bias
         wp, wc1 = self.p["aspp.global_avg_pool.1.weight"], self.p["aspp.conv1.weight"]
@@ -847,11 +776,10 @@ class Engine:
             prm, prv = self.buf.get("aspp.bn_after_pool.running_mean"), self.buf.get("aspp.bn_after_pool.running_var")
             if training:
                 pv, pst = ops.norm_fwd(zp, 1, B, c, c, pg, pb_, True, None, None, 1e-5, prm if upd else None, prv if upd else None, 0.1)
-                nbt = self.buf.get("aspp.bn_after_pool.num_batches_tracked")
-                if upd and nbt is not None:
-                    ops.rec(lambda: nbt.add_(1))
+                if upd:
+                    self._count_batch("aspp.bn_after_pool")
             else:
-                pst = torch.stack([prm, torch.rsqrt(prv + 1e-5)], 1).reshape(-1).contiguous()
+                pst = self._eval_stats(prm, prv)
                 pv = ops.norm_apply(zp, pst, 1, B, c, c, pg, pb_, True)
         else:
             pv = ops.relu_fwd(zp)
@@ -950,7 +878,7 @@ class Engine:
         """whether the V-Net's block_one runs as _first_block: bf16, a normalisation with batch statistics, the 1 -> 16 layer, and at
         most 16 samples (dycon_first_block_bwd refuses more)"""
         w1 = self.p["block_one.conv.0.weight"]
-        return (self.fuse_first and self.dtype == torch.bfloat16 and nk != "none" and not (nk == "bn" and not training)
+        return (self.dtype == torch.bfloat16 and nk != "none" and not (nk == "bn" and not training)
                 and w1.shape[0] == 16 and w1.shape[1] == 1 and x.shape[0] <= 16)
 
     def _vnet(self, x, training):
@@ -980,17 +908,11 @@ class Engine:
             x1 = self._first_block("block_one", x, nk, training)
         else:
             x1 = block("block_one", x, 1, first=True)
-        hook = self.stage_hook if self.stage_hook is not None else (lambda name: None)
-        hook("x1")
         self.pack_ready()            # (repack with early="block_one.": every other layer's operands were packed on a helper stream)
         x2 = block("block_two", down("block_one_dw", x1), 2)
-        hook("x2")
         x3 = block("block_three", down("block_two_dw", x2), 3)
-        hook("x3")
         x4 = block("block_four", down("block_three_dw", x3), 3)
-        hook("x4")
         x5 = block("block_five", down("block_four_dw", x4), 3, drop=("drop5", 0))   # + Dropout3d, VNet.py:195-196
-        hook("x5")
         x5_ready = self._mark_ready()
         u = up("block_five_up", x5, x4)
         u = up("block_six_up", block("block_six", u, 3), x3)
@@ -999,7 +921,7 @@ class Engine:
         w9, wo = self.p["block_nine.conv.0.weight"], self.p["out_conv.weight"]
         head_ok = w9.shape[0] == 16 and wo.shape[0] == 2           # the fused kernels are written for 16 channels -> 2 classes
         bn_drop = nk == "bn" and self.dropout.mode != "off"        # per-sample Dropout3d masks under BatchNorm: unfused (see _norm)
-        if self.fuse_head and nk != "none" and head_ok and not bn_drop:   # block_nine's norm + ReLU + Dropout3d + out_conv in one pass
+        if nk != "none" and head_ok and not bn_drop:   # block_nine's norm + ReLU + Dropout3d + out_conv in one pass
             z9 = self._conv("block_nine.conv.0", u, "k3", norm_groups=ngroups(u, "block_nine.conv.0"))
             cs9 = self._channel_scale(z9.shape[0], z9.shape[-1], "drop9", 0.5, 1, z9.device)
             logits = self._norm_head("block_nine.conv.1", z9, nk, "out_conv", training=training, chan_scale=cs9)
@@ -1070,12 +992,6 @@ class Engine:
         self.tape, self.G = [], {}
         self._deferred = {}
         self._stat_parts = {}
-        if self.use_acc and not self.acc_external:        # stand-alone engine (module route, tests): own arena, cleared here
-            if self.acc_arena is None:
-                self.acc_arena = torch.empty(self.ACC_DOUBLES, dtype=torch.float64, device=x.device)
-            arena = self.acc_arena
-            ops.rec(lambda: arena.zero_())
-        self._acc_off = 0
         if x.dtype != self.dtype:
             x = ops.cast(x, self.dtype)
         if self.net_type == "vnet":
@@ -1126,6 +1042,4 @@ class Engine:
             ops.fork(self.wgrad_stream, cs)                   # all parameter gradients are complete behind this point
             if self.wgrad_stream2 is not None:
                 ops.fork(self.wgrad_stream2, cs)
-            if self.wgrad_stream3 is not None and self.wgrad_stream3 is not self.feat_stream:
-                ops.fork(self.wgrad_stream3, cs)
         self.tape, self.G = [], {}

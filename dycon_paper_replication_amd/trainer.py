@@ -18,7 +18,6 @@ from __future__ import annotations
 
 import contextlib
 import math
-import os
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, Optional
@@ -26,7 +25,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _lib, ops
-from .engine import ABLATE, ABLATE_N, DropoutSpec, Engine, param_spec, projection_buffers
+from .engine import DropoutSpec, Engine, param_spec, projection_buffers
 from .networks.net_factory_3d import net_factory_3d
 from .utils import ramps
 from .utils.dycon_losses import adaptive_beta, sigmoid_rampup
@@ -71,22 +70,9 @@ class TrainConfig:
     strict_nan_check: bool = True       # read the NaN/Inf flag every step, as the reference does
     global_batch_losses: bool = True    # DDP: all-reduce the Dice / FeCL-cross sums (exact global-batch semantics)
     overlap_teacher: bool = True        # teacher forward on a second HIP stream, concurrent with the student forward
-    teacher_after: Optional[str] = None # V-Net: start the teacher forward only when the student's encoder tensor x1..x5 is enqueued (phase shift
-                                        # of the two forwards: the teacher's HBM-bound top level beside the student's latency-bound deep levels)
-    teacher_priority: int = -1          # HIP priority of that stream (-1 high, 0 normal, 1 low): high measured 0.06 ms/step faster
-    overlap_wgrad: bool = True          # weight-gradient launches of the backward on a second HIP stream (off the dgrad chain)
-    wgrad_two_streams: bool = True      # ... alternating with the teacher's stream, which is idle during the backward
+    overlap_wgrad: bool = True          # weight-gradient launches of the backward on side streams (off the dgrad chain): a stream of
+                                        # their own, alternating with the teacher's (idle during the backward) where that one exists
     overlap_features: bool = True       # feature branch (projection head, embeddings, FeCL forward + backward) on its own stream
-    split_repack: bool = True           # the student's weight repack off the head of the dependent chain (Engine.repack)
-    conv_stats: bool = False            # 48^3 level: norm statistics taken by the persistent convolution (measured neutral: off)
-    conv_stats96: bool = False          # 96^3 level (block_one, block_nine): the same.  Saves a 113 MB statistics pass per site, but the
-                                        # epilogue costs the convolutions as much (conv_k3_c1 38 -> 78 us, conv_k3_p16 74 -> 90 us per launch
-                                        # against 4 x 20 us of statistics launches): step unchanged over three A/B pairs -- off
-    one_pass_first: bool = True         # block_one's backward as one pass over (x, z, gy) (Engine.one_pass_first)
-    fuse_first: bool = True             # V-Net: block_one's norm backward inside the first layer's weight gradient (Engine._first_block)
-    fuse_head: bool = True              # V-Net: out_conv fused into block_nine's normalisation passes (Engine._norm_head)
-    fuse_finish: bool = False           # small levels: split-K finish of a convolution done by the one-launch norm that follows (Engine.fuse_finish)
-    norm_accumulators: bool = False     # two-launch norms through double-atomic accumulators (measured slower: DESIGN.md section 9)
     ddp_force: bool = False             # run the data-parallel exchange with a ONE-rank process group as well (RCCL test on one GPU)
     replay: bool = True                 # after two eager steps of a given input signature, record the step's launch list once and
                                         # re-issue it with patched scalars (the step is host-enqueue-bound: see DyconTrainer.step);
@@ -171,20 +157,6 @@ class DyconTrainer:
         self._fast_math = cfg.dtype == torch.bfloat16     # voxel-loss exp / log by the hardware sequences; fp32 = parity mode, libm
         self.s_eng = Engine(cfg.model, self.p, self.g, self.s_buf, cfg.dtype, cfg.feature_scaler, cfg.normalization)
         self.t_eng = Engine(cfg.model, self.t, None, self.t_buf, cfg.dtype, cfg.feature_scaler, cfg.normalization)
-        self.s_eng.fuse_finish = self.t_eng.fuse_finish = cfg.fuse_finish
-        self.s_eng.fuse_head = self.t_eng.fuse_head = cfg.fuse_head
-        self.s_eng.fuse_first = self.t_eng.fuse_first = cfg.fuse_first
-        self.s_eng.one_pass_first = self.t_eng.one_pass_first = cfg.one_pass_first
-        self.s_eng.conv_stats = self.t_eng.conv_stats = cfg.conv_stats
-        self.s_eng.conv_stats96 = self.t_eng.conv_stats96 = cfg.conv_stats96
-        # accumulator form of the norms (engine.use_acc; measured slower, off by default): one arena of zeroed doubles per step,
-        # shared by both nets and cleared by ONE launch at the start of the step, before the teacher stream forks
-        self.acc_arena = None
-        if cfg.norm_accumulators:
-            self.acc_arena = torch.zeros(2 * Engine.ACC_DOUBLES, dtype=torch.float64, device=self.device)
-            for eng, half in ((self.s_eng, 0), (self.t_eng, 1)):
-                eng.acc_arena = self.acc_arena[half * Engine.ACC_DOUBLES:(half + 1) * Engine.ACC_DOUBLES]
-                eng.acc_external, eng.use_acc = True, True
         self.iter_num = 0
         self.lr = cfg.base_lr * (self.world if self.world > 1 else 1)   # LR x n_gpu, train_DyCON_BraTS19.py:108-110
         self.base_lr = self.lr
@@ -199,44 +171,36 @@ class DyconTrainer:
         # of the step, when the copy has long completed -- the host never waits for the backward, the GPU never runs dry
         self.flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self.flag_evt = torch.cuda.Event()
-        # HIP priorities of the side streams (teacher, weight gradients, features).  Measured (profiles/r03_stream_scheduling.txt, pairs on
-        # one box): the TEACHER's stream at high priority takes 0.06 ms off the step (4.90 -> 4.84 ms) -- its forward ends earlier and
-        # leaves the student's large levels alone sooner; high priority for the weight-gradient or feature stream returns nothing, low
-        # priority for the side streams costs 0.03 ms (and round 2 had the MAIN stream at high priority at 8.2 ms against 5.8).
-        # DYCON_SIDE_PRIORITY="t,w,f" overrides (diagnostic).
-        prios = [cfg.teacher_priority, 0, 0]
-        if os.environ.get("DYCON_SIDE_PRIORITY"):
-            prios = [int(v) for v in os.environ["DYCON_SIDE_PRIORITY"].split(",")]
-            prios = (prios * 3)[:3] if len(prios) == 1 else (prios + [0, 0, 0])[:3]
-
-        def side_stream(prio):
-            if prio == 0:
-                return torch.cuda.Stream(device=self.device)
+        # HIP priorities of the side streams: teacher high (-1), weight gradients and features normal (0).  Measured
+        # (profiles/r03_stream_scheduling.txt, pairs on one box): the TEACHER's stream at high priority takes 0.06 ms off the step
+        # (4.90 -> 4.84 ms) -- its forward ends earlier and leaves the student's large levels alone sooner; high priority for the
+        # weight-gradient or feature stream returns nothing, low priority for the side streams costs 0.03 ms (and round 2 had the
+        # MAIN stream at high priority at 8.2 ms against 5.8).
+        def high_priority_stream():
             import ctypes
             h = _lib.hip()
             sp = ctypes.c_void_p()
             h.hipStreamCreateWithPriority.restype = ctypes.c_int
             h.hipStreamCreateWithPriority.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint, ctypes.c_int]
             with torch.cuda.device(self.device):
-                rc = h.hipStreamCreateWithPriority(ctypes.byref(sp), 1, prio)      # hipStreamNonBlocking
+                rc = h.hipStreamCreateWithPriority(ctypes.byref(sp), 1, -1)      # hipStreamNonBlocking
             if rc:
-                raise RuntimeError(f"hipStreamCreateWithPriority({prio}) failed: {rc}")
+                raise RuntimeError(f"hipStreamCreateWithPriority(-1) failed: {rc}")
             return torch.cuda.ExternalStream(sp.value, device=self.device)
-        self.side = side_stream(prios[0])
+        self.side = high_priority_stream()
         if cfg.overlap_wgrad:
-            self.s_eng.wgrad_stream = side_stream(prios[1])
+            self.s_eng.wgrad_stream = torch.cuda.Stream(device=self.device)
         # The feature branch -- projection head -> normalised embeddings -> FeCL, forward and backward -- meets the segmentation
         # branch only at the bottleneck tensor and in the scalar loss: it runs on a third stream, beside the decoder.
         # the teacher's stream is idle during the backward: the convolutions' weight gradients alternate between it and the weight-gradient
         # stream (4.781 -> 4.755 ms/step over three pairs, profiles/r03_stream_scheduling.txt); still four streams in all
-        if cfg.overlap_wgrad and cfg.overlap_teacher and cfg.wgrad_two_streams and os.environ.get("DYCON_WGRAD_TWO_STREAMS", "1") == "1":
+        if cfg.overlap_wgrad and cfg.overlap_teacher:
             self.s_eng.wgrad_stream2 = self.side
         # the teacher's projection head depends on its bottleneck only: it runs beside the teacher's decoder on the weight-gradient
         # stream (idle during the forwards), so the teacher's chain ends one head earlier
-        if (cfg.overlap_teacher and cfg.overlap_features and self.s_eng.wgrad_stream is not None
-                and os.environ.get("DYCON_TEACHER_HEAD_STREAM", "1") == "1"):
+        if cfg.overlap_teacher and cfg.overlap_features and self.s_eng.wgrad_stream is not None:
             self.t_eng.feat_stream = self.s_eng.wgrad_stream
-        self.feat = side_stream(prios[2]) if cfg.overlap_features else None
+        self.feat = torch.cuda.Stream(device=self.device) if cfg.overlap_features else None
         # HIP multiplexes a process's streams onto 4 hardware queues.  The data-parallel run adds torch's collective stream: with
         # five or more busy streams two of them SHARE a queue and serialise (profiles/r03_ddp_one_rank_trace.txt: the teacher forward and
         # the weight-gradient launches, +0.28 ms/step), and raising GPU_MAX_HW_QUEUES to 8 oversubscribes the queues (7.4 ms/step).
@@ -246,8 +210,6 @@ class DyconTrainer:
         if self.ddp and self.feat is not None and cfg.overlap_teacher:
             self.feat = self.side
         self.s_eng.feat_stream = self.feat
-        if self.s_eng.wgrad_stream2 is not None and self.feat is not None and os.environ.get("DYCON_WGRAD_THREE_STREAMS") == "1":
-            self.s_eng.wgrad_stream3 = self.feat        # (diagnostic)
         self.marks = None            # see _mark
         self._rp = None              # recorded step: dict(sig, rec, by_name, it, out, vol, lab)
         self._eager_seen = {}
@@ -258,8 +220,7 @@ class DyconTrainer:
         self.buckets = []
         if self.ddp:
             heads = [k for k in order if offs[k] < self.n_sgd and len(spec[k]) == 5]   # conv weights: notified by the backward
-            cuts = bucket_cuts([offs[k] for k in heads], self.n_sgd, nb=4,
-                               tail_frac=float(os.environ.get("DYCON_DDP_TAIL_FRAC", "0.06")))
+            cuts = bucket_cuts([offs[k] for k in heads], self.n_sgd, nb=4)
             by_off = {offs[k]: k for k in heads}
             self.buckets = [(by_off[lo], lo, hi) for lo, hi in zip(cuts[:-1], cuts[1:])]
             self._bucket_of = {name: (lo, hi) for name, lo, hi in self.buckets}
@@ -428,9 +389,9 @@ class DyconTrainer:
         self._mark("step_begin")
         # coef = d total / d (ce, dice_fg, dice_mc, cons, uncl | fecl): host-known, so it is written at the head of the step -- the
         # feature branch's backward (FeCL gradient, embeddings, projection head) then depends on nothing but its own forward and MAY
-        # start as soon as that is done, beside the student's decoder, instead of behind the scalar end of the loss on the main stream
-        # (DYCON_FEAT_BWD_EARLY=1).  Measured: 15.07 -> 15.00 ms at 112 x 112 x 80, where that branch is the step's critical path, but
-        # 4.45 -> 4.48 ms on the headline step (it then shares the CUs with the student's HBM-bound top level): off by default.
+        # start as soon as that is done, beside the student's decoder, instead of behind the scalar end of the loss on the main stream.
+        # Measured: 15.07 -> 15.00 ms at 112 x 112 x 80, where that branch is the step's critical path, but 4.45 -> 4.48 ms on the
+        # headline step (it then shares the CUs with the student's HBM-bound top level): so the feature stream waits for main first.
         # Means over equal shards (CE, cons, UnCL, FeCL student part) become global through the 1/world arena average;
         # the two global-ratio terms are differentiated w.r.t. LOCAL voxels and must be SUMMED over ranks -> x world.
         glob = self.ddp and c.global_batch_losses
@@ -439,12 +400,9 @@ class DyconTrainer:
         ops.set_scalars(self.coef, [c.l_weight, c.l_weight * (1 - dice_kind) * gw, c.l_weight * dice_kind * gw, cw,
                                     c.u_weight, c.u_weight])
         ops.rec(lambda: self.sumsq.zero_())          # (its first use is mid-backward at the earliest)
-        if self.acc_arena is not None:
-            arena = self.acc_arena
-            ops.rec(lambda: arena.zero_())
         # all weight packs of the step (student fwd + dgrad, teacher fwd): one launch per net; the student's is split so that only
         # block_one's operands are packed in front of the first convolution, the rest on the (idle) weight-gradient stream
-        if c.split_repack and self.s_eng.wgrad_stream is not None:
+        if self.s_eng.wgrad_stream is not None:
             self.s_eng.repack(early="block_one.", helper=self.s_eng.wgrad_stream)
         else:
             self.s_eng.repack()
@@ -457,62 +415,24 @@ class DyconTrainer:
         # small, launch-latency-bound kernels of the deep levels (6^3, 12^3: 50-100 workgroups on 256 CUs) of the two nets overlap.
         t_train = c.teacher_mode == "train"
         main = self._main = ops.cur_stream()
-        if "teacher" in ABLATE:      # tools/ablate.py (timing experiment only)
-            s_logits, s_feat, _ = self.s_eng.forward(x, training=True, record=True, dropout=s_drop, update_bn=True)
-            t_logits, t_feat = s_logits, s_feat
-        elif c.overlap_teacher and c.teacher_after and c.model == "vnet":
-            # phase-shifted forwards: the student's is enqueued first and records an event when the chosen encoder tensor is enqueued;
-            # the teacher's weight packs start at once, its forward behind that event
+        if c.overlap_teacher:
             side = self.side
             ops.fork(main, side)
-            with ops.on_stream(self.side):
-                self.t_eng.repack()
-            gate = ops.Event()
-            self.s_eng.stage_hook = lambda name: gate.record(main) if name == c.teacher_after else None
-            s_logits, s_feat, _ = self.s_eng.forward(x, training=True, record=True, dropout=s_drop, update_bn=True)   # :304
-            self.s_eng.stage_hook = None
-            with ops.on_stream(self.side):
-                gate.wait(side)
-                t_logits, t_feat, _ = self.t_eng.forward(x_t, training=t_train, record=False, dropout=t_drop, update_bn=t_train)
-                self._mark("teacher_fwd_end")
-            x_t.record_stream(self.side)
-        elif c.overlap_teacher:
-            side = self.side
-            ops.fork(main, side)
-            head_start = os.environ.get("DYCON_STUDENT_AFTER")      # diagnostic: the student's forward waits for the teacher's x1..x5
-            gate = ops.Event() if head_start else None
             with ops.on_stream(self.side):
                 # the teacher's packs belong to its stream (the EMA update that changed them precedes the fork).  Splitting them like the
-                # student's (block_one's operands first, the rest on an idle stream) measured neutral to +0.01 ms: off (DYCON_TEACHER_SPLIT_PACK)
-                if c.split_repack and self.feat is not None and self.feat is not self.side and os.environ.get("DYCON_TEACHER_SPLIT_PACK", "0") == "1":
-                    self.t_eng.repack(early="block_one.", helper=self.feat)
-                else:
-                    self.t_eng.repack()
-                if gate is not None:
-                    self.t_eng.stage_hook = lambda name: gate.record(side) if name == head_start else None
+                # student's (block_one's operands first, the rest on an idle stream) measured neutral to +0.01 ms: one launch
+                self.t_eng.repack()
                 t_logits, t_feat, _ = self.t_eng.forward(x_t, training=t_train, record=False, dropout=t_drop, update_bn=t_train)
-                self.t_eng.stage_hook = None
                 self._mark("teacher_fwd_end")
-            if gate is not None:
-                gate.wait(main)
             x_t.record_stream(self.side)
-        if "teacher" not in ABLATE and not (c.overlap_teacher and c.teacher_after and c.model == "vnet"):
-            s_logits, s_feat, _ = self.s_eng.forward(x, training=True, record=True, dropout=s_drop, update_bn=True)   # :304
-        if "teacher" in ABLATE:
-            pass
-        elif c.overlap_teacher:
+        s_logits, s_feat, _ = self.s_eng.forward(x, training=True, record=True, dropout=s_drop, update_bn=True)   # :304
+        if c.overlap_teacher:
             ops.fork(side, main)
             t_logits.record_stream(main)
             t_feat.record_stream(main)
         else:
             t_logits, t_feat, _ = self.t_eng.forward(x_t, training=t_train, record=False, dropout=t_drop, update_bn=t_train)
 
-        if "extra_launches" in ABLATE:     # tools/ablate.py: is the step bound by the dispatch rate?  N trivial launches on an idle stream
-            if not hasattr(self, "_xs"):
-                self._xs, self._xbuf = torch.cuda.Stream(device=self.device), torch.zeros(8, device=self.device)
-            with ops.on_stream(self._xs, light=True):
-                for _ in range(ABLATE_N):
-                    ops.set_scalars(self._xbuf, [0.0])
         self._mark("student_fwd_end")
         # ---- losses (:308-357)
         world = self.world
@@ -529,13 +449,10 @@ class DyconTrainer:
                 feat, src = self.feat, (self.side if c.overlap_teacher else main)
                 if self.t_eng.feat_stream is not None and self.t_eng.feat_stream is not src:
                     # the teacher's projection head ran beside its decoder on another stream.  The embeddings and FeCL still wait for the
-                    # END of the teacher's forward as well: starting them as soon as the head is done (DYCON_FECL_EARLY=1, i.e. while both
-                    # decoders are in their latency-bound deep levels) measured 0.04 ms SLOWER than beside the student's HBM-bound top level
+                    # END of the teacher's forward as well: starting them as soon as the head is done (i.e. while both decoders are
+                    # in their latency-bound deep levels) measured 0.04 ms SLOWER than beside the student's HBM-bound top level
                     ops.fork(self.t_eng.feat_stream, feat)
-                    if os.environ.get("DYCON_FECL_EARLY", "0") != "1":
-                        ops.fork(src, feat)
-                else:
-                    ops.fork(src, feat)
+                ops.fork(src, feat)
                 t_feat.record_stream(self.feat)
             s_emb, s_nrm = ops.l2norm_fwd(s_feat.reshape(B, -1, s_feat.shape[-1]))          # :316-319
             t_emb, _ = ops.l2norm_fwd(t_feat.reshape(B, -1, t_feat.shape[-1]))              # :321-323
@@ -573,14 +490,11 @@ class DyconTrainer:
         g_logits = ops.seg_losses_bwd(s_logits, t_logits, label, LB, beta, sums, self.coef, cons_kind, fast=self._fast_math)
         if gmb:    # FeCL's gradient into the student's logits through u (the 8 voxels of each patch), before the backward reads g_logits
             ops.gambling_uncertainty_bwd(s_logits, k, gu, g_logits, fast=self._fast_math)
-        if self.feat is not None and (glob or gmb or os.environ.get("DYCON_FEAT_BWD_EARLY", "0") != "1"):
-            ops.fork(main, feat)       # DDP: the all-reduced FeCL sums (cross-branch count) are exchanged on main; gambling: the finalize
+        if self.feat is not None:
+            ops.fork(main, feat)       # (needed by DDP: the all-reduced FeCL sums are exchanged on main; by gambling: the finalize)
         with fctx():
-            if "feat_bwd" in ABLATE:     # tools/ablate.py (timing only): the feature branch's loss backward switched off
-                g_feat = torch.zeros_like(s_feat)
-            else:
-                g_emb = ops.fecl_bwd(*fargs, float(gw), fst, self.coef[5:6])
-                g_feat = ops.l2norm_bwd(s_emb, s_nrm, g_emb).reshape(s_feat.shape)
+            g_emb = ops.fecl_bwd(*fargs, float(gw), fst, self.coef[5:6])
+            g_feat = ops.l2norm_bwd(s_emb, s_nrm, g_emb).reshape(s_feat.shape)
         self.s_eng.backward(g_logits, g_feat)            # head entries replay on self.feat, joins at the bottleneck gradient
 
         # ---- all-reduce, clip, SGD, EMA (:368-372)

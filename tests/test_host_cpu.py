@@ -99,3 +99,20 @@ def test_vnet_param_spec_all_normalizations(norm):
     bufs = [k for k, _ in net.named_buffers()]
     assert bufs == list(net_buffers("vnet", norm))
     assert ("block_one.conv.1.running_mean" in bufs) == (norm == "batchnorm")
+
+
+def test_step_has_no_outside_switches():
+    """Nothing in a step can be changed from outside the process: the package reads the environment in ONE place (DYCON_LIB in _lib.py:
+    which shared library is loaded, not what a step does), and the switches TrainConfig offers are exactly the ones written down here."""
+    import dataclasses
+    pkg = os.path.join(ROOT, "dycon_paper_replication_amd")
+    hits = []
+    for d, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                path = os.path.join(d, f)
+                hits += [(os.path.relpath(path, pkg), line.strip()) for line in open(path) if "environ" in line or "getenv" in line]
+    assert len(hits) == 1 and hits[0][0] == "_lib.py" and hits[0][1].startswith('LIB_PATH = os.environ.get("DYCON_LIB"'), hits
+    bools = {f.name for f in dataclasses.fields(TrainConfig) if isinstance(f.default, bool)}
+    assert bools == {"poly_lr", "strict_nan_check", "global_batch_losses", "overlap_teacher", "overlap_wgrad", "overlap_features",
+                     "use_aspp", "ddp_force", "replay"}, bools

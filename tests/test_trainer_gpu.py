@@ -24,13 +24,18 @@ def _stats(t):
     return np.array([t.sum().item(), t.abs().sum().item(), (t * t).sum().item()])
 
 
+@pytest.mark.parametrize("streams", ["overlapped", "single"])
 @pytest.mark.parametrize("kind", ["unet", "vnet"])
-def test_two_step_trace_vs_reference(kind):
+def test_two_step_trace_vs_reference(kind, streams):
+    """streams "single": the same step with every launch on one stream (no teacher, weight-gradient or feature side stream) -- a
+    failure of "overlapped" alone is a race, a failure of both an arithmetic defect"""
     g = load_golden(f"step_{kind}")
     net_type = "unet_3D" if kind == "unet" else "vnet"
     mk = ON.make_unet_params if kind == "unet" else ON.make_vnet_params
     s0, s1 = [int(v) for v in g["seeds"]]
-    cfg = TrainConfig(model=net_type, labeled_bs=int(g["LB"]), batch_size=int(g["B"]), dtype=torch.float32, feature_scaler=2)
+    overlap = streams == "overlapped"
+    cfg = TrainConfig(model=net_type, labeled_bs=int(g["LB"]), batch_size=int(g["B"]), dtype=torch.float32, feature_scaler=2,
+                      overlap_teacher=overlap, overlap_wgrad=overlap, overlap_features=overlap)
     tr = DyconTrainer(cfg, DEV, student_init=mk(s0), teacher_init=mk(s1))
     names = list(g["param_names"])
     assert names == tr.names

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of TrainConfig settings on the bench configuration, every case in a FRESH process (the allocator state of a process moves the
-step time by up to 20 %), repeated:   python tools/ab.py fuse_finish=False fuse_finish=True [--reps 2] [--steps 100]"""
+step time by up to 20 %), repeated:   python tools/ab.py overlap_features=False overlap_features=True [--reps 2] [--steps 100]"""
 import os
 import subprocess
 import sys
