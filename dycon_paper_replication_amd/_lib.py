@@ -26,11 +26,15 @@ SIGNATURES = {
     "dycon_pack_batch": (I, [P, I, I, P]),
     "dycon_pack_tcn": (I, [P, P, I, I, I, I, L, L, L, L, I, P]),
     "dycon_conv_gemm_workspace": (Z, [I, I, I, I, I, I, I, I, I]),
+    "dycon_conv_gemm_plan": (I, [I, I, I, I, I, I, I, I, I, I, I, P]),
+    "dycon_conv_kernel_name": (C.c_char_p, [I]),
+    "dycon_conv_region_name": (C.c_char_p, [P]),
     "dycon_conv_gemm": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, Z, P]),
     "dycon_conv_gemm_splits": (I, [I, I, I, I, I, I, I, I, I]),
     "dycon_conv_gemm_ex": (I, [P, P, P, P, I, I, I, I, I, I, I, I, I, I, I, P, Z, I, P]),
     "dycon_conv_direct": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, I, P]),
     "dycon_conv_wgrad_workspace": (Z, [I, I, I, I, I, I, I]),
+    "dycon_conv_wgrad_name": (C.c_char_p, [I, I, I, I, I, I, I, I, I]),
     "dycon_conv_wgrad": (I, [P, I, P, I, P, P, I, I, I, I, I, I, I, L, L, L, P, Z, P]),
     "dycon_colsum_workspace": (Z, [L, I]),
     "dycon_colsum": (I, [P, I, P, L, I, P, Z, P]),
@@ -134,6 +138,15 @@ SIGNATURES = {
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),
     "dycon_kernel_timing_name": (C.c_char_p, [I]),
 }
+
+
+class ConvPlan(C.Structure):
+    """dycon_conv_plan_t (family: CONV_NONE .. CONV_GEMM, weights: CONV_W_*)"""
+    _fields_ = [("family", I), ("splits", I), ("chunks", I), ("weights", I), ("workspace", Z)]
+
+
+CONV_NONE, CONV_C1, CONV_P16, CONV_P32, CONV_LDS, CONV_HALO, CONV_TILE, CONV_GEMM = range(8)      # DYCON_CONV_*
+CONV_W_FRAG, CONV_W_CHUNK16 = 0, 1
 
 
 class View(C.Structure):

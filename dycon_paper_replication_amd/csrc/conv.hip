@@ -2888,11 +2888,6 @@ static SplitK splitk_plan(int dtype, int mode, int scatter, long long M, int N, 
     p.splits = (nKC + p.kc_per_split - 1) / p.kc_per_split;
     return p;
 }
-
-// LDS-tiled kernel for the small levels: bf16, k3, channel counts that fill its 32-wide k-steps and 128-wide column tiles
-static bool conv_tile_ok(int dtype, int mode, int scatter, long long DHW, int Cin, int N) {
-    return dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && Cin % 32 == 0 && N % CT_BN == 0 && Cin >= 64 && DHW < 13824;
-}
 static SplitK conv_tile_plan(long long M, int N, int Cin) {
     constexpr long long target_wgs = 512;
     const int nKC = 27 * Cin / 32;
@@ -2907,13 +2902,108 @@ static SplitK conv_tile_plan(long long M, int N, int Cin) {
     p.splits = (nKC + p.kc_per_split - 1) / p.kc_per_split;
     return p;
 }
-// one-launch kernel for the small levels (conv_k3_halo_kernel: the split of conv_tile_plan done inside the workgroup, no slab, same
-// bits): taken ahead of conv_k3_tile for 128 input channels when the plan has at most 4 ranges (the 12^3 and 14x14x10 levels at
-// B = 4; a 64-column range per wave, for 5..8 ranges, spills at the register budget of two workgroups per CU).  At Cin = 256 (the
-// 6^3 level) a 64-column halo kernel measured even with conv_k3_tile<2> + finish (19.3 against 19.2 us): each
-// workgroup there streams 884 KB of weights and only 128 workgroups run; that level keeps its split-K slabs.
-static bool conv_halo_ok(int dtype, int mode, int scatter, long long M, long long DHW, int Cin, int N) {
-    return conv_tile_ok(dtype, mode, scatter, DHW, Cin, N) && Cin == CH_CIN && conv_tile_plan(M, N, Cin).splits <= CH_MAXS;
+
+// ---- the forward plan: which kernel serves a convolution, with which grid, split and workspace.  The launch (conv_fwd_launch), the
+// size / split / chunk queries and dycon_conv_gemm_plan (what Python reads) all take their answer from here; nothing else decides.
+constexpr long long CONV_LDS_MIN_VOXELS = 13824;      // 24^3: from here up the bf16 k=3 levels run on the LDS-halo kernels
+// first layer on the matrix cores (conv_k3_c1_kernel): one input channel, exempt from the fragment-width check below
+static bool conv_first_layer(int dtype, int mode, int scatter, int Di, int Hi, int Wi, int Cin, int Cout) {
+    return dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && Cin == 1 && (Cout == 16 || Cout == 32 || Cout == 64) &&
+           (long long)Di * Hi * Wi >= CONV_LDS_MIN_VOXELS;
+}
+// The argument checks of dycon_conv_gemm, stated once: the launch reports the first that fails (fmt, with arg), the plan marks the
+// shape refused.  fmt == nullptr: the shape is taken.
+struct ConvRefusal { const char* fmt; int arg; };
+static ConvRefusal conv_refusal(int dtype, int mode, int scatter, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout) {
+    if (!(B > 0 && Di > 0 && Hi > 0 && Wi > 0 && Cin > 0 && N > 0 && Cout > 0)) return {"conv_gemm: bad shape", 0};
+    if (mode < 0 || mode > 2) return {"conv_gemm: bad mode %d", mode};
+    if (!conv_first_layer(dtype, mode, scatter, Di, Hi, Wi, Cin, Cout) && Cin % (dtype == DYCON_BF16 ? 8 : 4) != 0)
+        return {"conv_gemm: Cin=%d not a multiple of the fragment width", Cin};
+    if (N % 16 != 0) return {"conv_gemm: N=%d not a multiple of 16 (use dycon_conv_direct)", N};
+    if (scatter && !(mode == DYCON_CONV_1X1 && N == 8 * Cout)) return {"conv_gemm: scatter needs mode 1x1 and N == 8*Cout", 0};
+    if (!scatter && N != Cout) return {"conv_gemm: N must equal Cout without scatter", 0};
+    if (mode == DYCON_CONV_K2S2 && (Di % 2 || Hi % 2 || Wi % 2)) return {"conv_gemm: k2s2 needs even dims", 0};
+    return {nullptr, 0};
+}
+struct ConvPlan {
+    int family = DYCON_CONV_NONE;   // DYCON_CONV_* of the ladder below (DYCON_CONV_NONE: no output rows at all)
+    int variant = 0;                // c1: Cout / 16; halo: 64-column ranges per wave; tile: 32-channel k-steps per iteration
+    int ck = 0, ntb = 0;            // lds: channels per k-step, 16-column tiles per workgroup
+    bool wide = false;              // lds: 8 waves per workgroup
+    int tz = 0, ty = 0, tx = 0, nTiles = 0;       // voxel tiles of the family
+    dim3 grid;                      // .z = sk.splits on the slab families (1 at launch when the caller gives no workspace)
+    long long M = 0;                // output rows
+    SplitK sk{1, 0};                // k ranges: slabs of tile / gemm, ranges summed inside the workgroup of halo
+    int splits = 1;                 // slabs the caller sees (> 1: workspace, finish or dycon_norm_fwd_slab)
+    size_t ws_bytes = 0;
+    int chunks = 0;                 // statistics rows per sample dycon_conv_gemm_stats writes (0: not served)
+    int weights = DYCON_CONV_W_FRAG;
+};
+static ConvPlan conv_fwd_plan(int dtype, int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout) {
+    ConvPlan p;
+    if (B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || N <= 0 || Cout <= 0 || mode < 0 || mode > 2) return p;
+    int Do, Ho, Wo;
+    row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
+    p.M = (long long)B * Do * Ho * Wo;
+    if (p.M <= 0) return p;           // k2s2 with a dimension of 1: no rows to tile or split
+    const long long DHW = (long long)Di * Hi * Wi;
+    const bool bf16_k3 = dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter;
+    const bool first_layer = conv_first_layer(dtype, mode, scatter, Di, Hi, Wi, Cin, Cout);
+    // large spatial levels, bf16: LDS-halo kernels
+    if (first_layer || (bf16_k3 && DHW >= CONV_LDS_MIN_VOXELS && (Cin == 16 || Cin == 48 || Cin % 32 == 0) && (Cout == 16 || Cout == 32 || Cout % 64 == 0 || Cout % 48 == 0))) {
+        p.tz = cdiv(Di, CL_TZ); p.ty = cdiv(Hi, CL_TY); p.tx = cdiv(Wi, CL_TX);
+        p.nTiles = B * p.tz * p.ty * p.tx;
+        if (first_layer || (Cin == 16 && Cout == 16)) {
+            // persistent kernels of the 16-channel level: 8 XCDs x up to 64 (p16: 2 per CU) / 128 (c1) workgroups
+            p.family = first_layer ? DYCON_CONV_C1 : DYCON_CONV_P16;
+            p.variant = Cout / 16;
+            p.grid = dim3(8 * min(cdiv(p.nTiles, 8), first_layer ? 128 : 32 * P16_WGS));
+            p.chunks = (Cout == 16 && !accumulate) ? (int)p.grid.x : 0;       // one row per workgroup
+        } else if (Cin == 32 && Cout == 32 && !accumulate && p.nTiles >= 1024) {
+            // 32 -> 32 with several tiles per CU: persistent kernel, weights stationary in LDS (one workgroup per CU)
+            // (a 32x32x16 MFMA form measured slower, 30.9 against 28.5 us per launch at 48^3, and was removed: DESIGN section 9)
+            p.family = DYCON_CONV_P32;
+            p.grid = dim3(8 * min(cdiv(p.nTiles, 8), 32));
+            p.chunks = (int)p.grid.x;
+        } else {
+            const int NT = Cout / 16;
+            p.family = DYCON_CONV_LDS;
+            p.ck = (Cin == 16 || Cin == 48) ? 16 : 32;
+            p.ntb = Cout % 64 == 0 ? CL_NTB64 : (Cout % 48 == 0 ? 3 : NT);
+            p.grid = dim3(p.nTiles, NT / p.ntb);
+            // at most one workgroup per CU: 8 waves, two per SIMD (a wave per SIMD is issue-bound)
+            p.wide = p.ck == 32 && p.ntb == 4 && (long long)p.nTiles * (NT / p.ntb) <= 256;
+            if (Cin == 48) p.weights = DYCON_CONV_W_CHUNK16;
+        }
+        return p;
+    }
+    // LDS-tiled kernels for the small levels: bf16, k3, channel counts that fill their 32-wide k-steps and 128-wide column tiles
+    if (bf16_k3 && Cin % 32 == 0 && N % CT_BN == 0 && Cin >= 64 && DHW < CONV_LDS_MIN_VOXELS) {
+        p.sk = conv_tile_plan(p.M, N, Cin);
+        // one-launch kernel (conv_k3_halo_kernel: the split of conv_tile_plan done inside the workgroup, no slab, same bits): taken
+        // ahead of conv_k3_tile for 128 input channels when the plan has at most 4 ranges (the 12^3 and 14x14x10 levels at B = 4; a
+        // 64-column range per wave, for 5..8 ranges, spills at the register budget of two workgroups per CU).  At Cin = 256 (the 6^3
+        // level) a 64-column halo kernel measured even with conv_k3_tile<2> + finish (19.3 against 19.2 us): each
+        // workgroup there streams 884 KB of weights and only 128 workgroups run; that level keeps its split-K slabs.
+        if (Cin == CH_CIN && p.sk.splits <= CH_MAXS) {
+            p.family = DYCON_CONV_HALO;
+            p.variant = p.sk.splits > 2 ? 2 : 1;
+            p.tz = cdiv(Di, CH_T); p.ty = cdiv(Hi, CH_T); p.tx = cdiv(Wi, CH_T);
+            p.nTiles = B * p.tz * p.ty * p.tx;
+            p.grid = dim3(p.nTiles, N / 64);
+            return p;
+        }
+        p.family = DYCON_CONV_TILE;
+        p.variant = (Cin % 64 == 0 && p.sk.kc_per_split % 2 == 0) ? 2 : 1;
+        p.grid = dim3(cdiv(p.M, CT_BM), N / CT_BN, p.sk.splits);
+    } else {
+        p.family = DYCON_CONV_GEMM;
+        p.sk = splitk_plan(dtype, mode, scatter, p.M, N, Cin);
+        p.grid = dim3(cdiv(p.M, 64), cdiv((N + 15) / 16, NTB), p.sk.splits);
+    }
+    p.splits = p.sk.splits;
+    if (p.splits > 1) p.ws_bytes = (size_t)p.splits * p.M * N * sizeof(float);
+    return p;
 }
 
 extern "C" int dycon_pack_batch(const dycon_pack_job_t* jobs_dev, int njobs, int blocks_per_job, dycon_stream_t stream) {
@@ -2923,80 +3013,153 @@ extern "C" int dycon_pack_batch(const dycon_pack_job_t* jobs_dev, int njobs, int
     return DYCON_OK;
 }
 
+template <typename T>
+static void launch_splitk_finish(const float* slabs, const ConvPlan& p, int N, const float* bias, void* y, int accumulate, dycon_stream_t stream) {
+    long long blocks = (p.M * N / 4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    splitk_finish_kernel<T><<<(int)blocks, 256, 0, stream>>>(slabs, p.splits, p.M * N, N, bias, (T*)y, accumulate);
+}
+
+// slabs == nullptr: single pass (same result up to fp32 summation order)
 template <typename T, int MODE, bool SC>
-static void launch_gemm(const void* x, const void* wf, const float* bias, void* y, int accumulate, int B, int Di, int Hi,
-                        int Wi, int Cin, int N, int Cout, float* workspace, int defer_finish, dycon_stream_t stream) {
+static void launch_gemm(const ConvPlan& p, const void* x, const void* wf, const float* bias, void* y, int accumulate, int B, int Di, int Hi,
+                        int Wi, int Cin, int N, int Cout, float* slabs, int defer_finish, dycon_stream_t stream) {
     int Do, Ho, Wo;
     row_grid(MODE, Di, Hi, Wi, Do, Ho, Wo);
-    const long long M = (long long)B * Do * Ho * Wo;
     const int NT = (N + 15) / 16;
     const int Tn = MODE == DYCON_CONV_K3 ? 27 : MODE == DYCON_CONV_K2S2 ? 8 : 1;
     const int nKC = (Tn * Cin + Frag<T>::KC - 1) / Frag<T>::KC;
-    const SplitK sk = splitk_plan(sizeof(T) == 2 ? DYCON_BF16 : DYCON_F32, MODE, SC, M, N, Cin);
-    const bool split = sk.splits > 1 && workspace != nullptr;
-    dim3 grid(cdiv(M, 64), cdiv(NT, NTB), split ? sk.splits : 1);
-    conv_gemm_kernel<T, MODE, SC><<<grid, 256, 0, stream>>>((const T*)x, (const T*)wf, bias, (T*)y, B, Di, Hi, Wi, Cin, Do, Ho,
-                                                            Wo, N, Cout, NT, nKC, accumulate, split ? workspace : nullptr,
-                                                            sk.kc_per_split, split && defer_finish && N % 8 == 0);
-    if (split && !defer_finish) {
-        long long blocks = (M * N / 4 + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        splitk_finish_kernel<T><<<(int)blocks, 256, 0, stream>>>(workspace, sk.splits, M * N, N, bias, (T*)y, accumulate);
-    }
+    conv_gemm_kernel<T, MODE, SC><<<dim3(p.grid.x, p.grid.y, slabs ? p.splits : 1), 256, 0, stream>>>(
+        (const T*)x, (const T*)wf, bias, (T*)y, B, Di, Hi, Wi, Cin, Do, Ho, Wo, N, Cout, NT, nKC, accumulate, slabs, p.sk.kc_per_split,
+        slabs && defer_finish && N % 8 == 0);
+    if (slabs && !defer_finish) launch_splitk_finish<T>(slabs, p, N, bias, y, accumulate, stream);
 }
 
+extern "C" int dycon_conv_gemm_plan(int dtype, int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N,
+                                    int Cout, dycon_conv_plan_t* out) {
+    DYCON_REQUIRE(out, "conv_gemm_plan: null pointer");
+    const ConvPlan p = conv_fwd_plan(dtype, mode, scatter, accumulate, B, Di, Hi, Wi, Cin, N, Cout);
+    // (the older queries answer for a refused shape too, so the plan itself does not stop at one)
+    out->family = conv_refusal(dtype, mode, scatter, B, Di, Hi, Wi, Cin, N, Cout).fmt ? DYCON_CONV_NONE : p.family;
+    out->splits = p.splits;
+    out->chunks = p.chunks;
+    out->weights = p.weights;
+    out->workspace = p.ws_bytes;
+    return DYCON_OK;
+}
+
+extern "C" const char* dycon_conv_kernel_name(int family) {
+    static const char* const names[] = {"none", "conv_k3_c1", "conv_k3_p16", "conv_k3_p32", "conv_k3_lds", "conv_k3_halo", "conv_k3_tile", "conv_gemm"};
+    return family >= 0 && family <= DYCON_CONV_GEMM ? names[family] : "?";
+}
+// a profile's name for one call: the generic kernel with slabs is kernel + finish
+extern "C" const char* dycon_conv_region_name(const dycon_conv_plan_t* plan) {
+    if (!plan) return "?";
+    return plan->family == DYCON_CONV_GEMM && plan->splits > 1 ? "conv_gemm_splitk" : dycon_conv_kernel_name(plan->family);
+}
+
+// the three older queries: one field of the plan each (no accumulation; their callers pass N for a scatter, Cout == N otherwise)
 extern "C" size_t dycon_conv_gemm_workspace(int dtype, int mode, int scatter, int B, int Di, int Hi, int Wi, int Cin, int N) {
-    int Do, Ho, Wo;
-    row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
-    const long long M = (long long)B * Do * Ho * Wo;
-    if (conv_halo_ok(dtype, mode, scatter, M, (long long)Di * Hi * Wi, Cin, N)) return 0;
-    const SplitK sk = conv_tile_ok(dtype, mode, scatter, (long long)Di * Hi * Wi, Cin, N) ? conv_tile_plan(M, N, Cin)
-                                                                                       : splitk_plan(dtype, mode, scatter, M, N, Cin);
-    return sk.splits > 1 ? (size_t)sk.splits * M * N * sizeof(float) : 0;
+    return conv_fwd_plan(dtype, mode, scatter, 0, B, Di, Hi, Wi, Cin, N, scatter ? N / 8 : N).ws_bytes;
 }
-
 extern "C" int dycon_conv_gemm_splits(int dtype, int mode, int scatter, int B, int Di, int Hi, int Wi, int Cin, int N) {
-    int Do, Ho, Wo;
-    row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
-    const long long M = (long long)B * Do * Ho * Wo;
-    if (conv_halo_ok(dtype, mode, scatter, M, (long long)Di * Hi * Wi, Cin, N)) return 1;
-    const SplitK sk = conv_tile_ok(dtype, mode, scatter, (long long)Di * Hi * Wi, Cin, N) ? conv_tile_plan(M, N, Cin)
-                                                                                       : splitk_plan(dtype, mode, scatter, M, N, Cin);
-    return sk.splits;
+    return conv_fwd_plan(dtype, mode, scatter, 0, B, Di, Hi, Wi, Cin, N, scatter ? N / 8 : N).splits;
+}
+// rows per sample of the statistics partials a dycon_conv_gemm_stats call of this shape writes (0: shape not served)
+extern "C" int dycon_conv_stats_chunks(int dtype, int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
+    return conv_fwd_plan(dtype, mode, 0, 0, B, Di, Hi, Wi, Cin, Cout, Cout).chunks;
 }
 
+// Argument checks, the plan, one launch per family.  stat_part (dycon_conv_gemm_stats only, on a shape whose plan has chunks): the
+// persistent kernels also leave the statistics partials of their stored outputs there.
 // defer_finish = 1 (split-K shapes with a workspace only): leave the partial slabs in `workspace` and do NOT launch the finish --
 // the caller completes the convolution with dycon_norm_fwd_slab (bias, ordered sum, rounding, norm in one launch).
+static int conv_fwd_launch(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int mode, int scatter, int accumulate,
+                           int B, int Di, int Hi, int Wi, int Cin, int N, int Cout, float* workspace, size_t ws_bytes, int defer_finish,
+                           float* stat_part, dycon_stream_t stream) {
+    DYCON_REQUIRE(x && wfrag && y, "conv_gemm: null pointer");
+    const ConvRefusal no = conv_refusal(dtype, mode, scatter, B, Di, Hi, Wi, Cin, N, Cout);
+    DYCON_REQUIRE(!no.fmt, no.fmt, no.arg);
+    const ConvPlan p = conv_fwd_plan(dtype, mode, scatter, accumulate, B, Di, Hi, Wi, Cin, N, Cout);
+    DYCON_REQUIRE(!defer_finish || (!accumulate && workspace && p.splits > 1 && ws_bytes >= p.ws_bytes),
+                  "conv_gemm: defer_finish needs a split-K shape, its workspace and no accumulation");
+    const bf16 *xp = (const bf16*)x, *wp = (const bf16*)wfrag;
+    bf16* yp = (bf16*)y;
+    float* slabs = (p.splits > 1 && workspace && ws_bytes >= p.ws_bytes) ? workspace : nullptr;
+    switch (p.family) {
+    case DYCON_CONV_C1:
+#define DYCON_C1(NTV, STV) conv_k3_c1_kernel<NTV, STV><<<p.grid, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, p.tz, p.ty, p.tx, p.nTiles, accumulate, stat_part)
+        if (stat_part) DYCON_C1(1, true);
+        else if (p.variant == 1) DYCON_C1(1, false);
+        else if (p.variant == 2) DYCON_C1(2, false);
+        else DYCON_C1(4, false);
+#undef DYCON_C1
+        break;
+    case DYCON_CONV_P16:
+#define DYCON_P16(ACCV, STV) conv_k3_p16_kernel<P16_DEPTH, ACCV, STV><<<p.grid, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, p.tz, p.ty, p.tx, p.nTiles, stat_part)
+        if (accumulate) DYCON_P16(true, false);
+        else if (stat_part) DYCON_P16(false, true);
+        else DYCON_P16(false, false);
+#undef DYCON_P16
+        break;
+    case DYCON_CONV_P32:
+#define DYCON_P32(STV) conv_k3_p32_kernel<8, STV><<<p.grid, 64 * 8, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, p.tz, p.ty, p.tx, p.nTiles, stat_part)
+        if (stat_part) DYCON_P32(true); else DYCON_P32(false);
+#undef DYCON_P32
+        break;
+    case DYCON_CONV_LDS:
+#define DYCON_CL(CKV, NTBV, WMV) \
+    conv_k3_lds_kernel<CKV, NTBV, WMV><<<p.grid, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, Cin, Cout, Cout / 16, p.tz, p.ty, p.tx, accumulate)
+        if (p.ck == 16) {
+            if (p.ntb == 1) DYCON_CL(16, 1, 4); else if (p.ntb == 2) DYCON_CL(16, 2, 4); else if (p.ntb == 3) DYCON_CL(16, 3, 4); else DYCON_CL(16, 4, 2);
+        } else {
+            if (p.ntb == 1) DYCON_CL(32, 1, 4); else if (p.ntb == 2) DYCON_CL(32, 2, 4); else if (p.ntb == 3) DYCON_CL(32, 3, 4);
+            else if (p.wide)
+                conv_k3_lds_kernel<32, 4, 4, 8><<<p.grid, 512, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, Cin, Cout, Cout / 16, p.tz, p.ty, p.tx, accumulate);
+            else DYCON_CL(32, 4, 2);
+        }
+#undef DYCON_CL
+        break;
+    case DYCON_CONV_HALO:
+#define DYCON_CH(NJV) conv_k3_halo_kernel<NJV><<<p.grid, 64 * CH_NW, 0, stream>>>(xp, wp, bias, yp, Di, Hi, Wi, N, N / 16, p.tz, p.ty, p.tx, p.sk.splits, p.sk.kc_per_split, accumulate)
+        if (p.variant == 2) DYCON_CH(2); else DYCON_CH(1);
+#undef DYCON_CH
+        break;
+    case DYCON_CONV_TILE: {
+        const dim3 grid(p.grid.x, p.grid.y, slabs ? p.splits : 1);
+#define DYCON_CT(KV) conv_k3_tile_kernel<KV><<<grid, 256, 0, stream>>>(xp, wp, bias, yp, slabs, B, Di, Hi, Wi, Cin, N, N / 16, 27 * Cin / 32, p.sk.kc_per_split, accumulate, slabs && defer_finish ? 1 : 0)
+        if (p.variant == 2) DYCON_CT(2); else DYCON_CT(1);
+#undef DYCON_CT
+        DYCON_LAUNCH_CHECK();
+        if (slabs && !defer_finish) launch_splitk_finish<bf16>(slabs, p, N, bias, y, accumulate, stream);
+        break;
+    }
+    default:      // DYCON_CONV_GEMM: split-K only when the caller provides the slab workspace
+        DYCON_DISPATCH(dtype, {
+            if (scatter) launch_gemm<T, DYCON_CONV_1X1, true>(p, x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, slabs, defer_finish, stream);
+            else if (mode == DYCON_CONV_K3) launch_gemm<T, DYCON_CONV_K3, false>(p, x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, slabs, defer_finish, stream);
+            else if (mode == DYCON_CONV_K2S2) launch_gemm<T, DYCON_CONV_K2S2, false>(p, x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, slabs, defer_finish, stream);
+            else launch_gemm<T, DYCON_CONV_1X1, false>(p, x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, slabs, defer_finish, stream);
+        });
+    }
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
 extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int mode,
                                   int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout,
-                                  float* workspace, size_t ws_bytes, int defer_finish, dycon_stream_t stream);
+                                  float* workspace, size_t ws_bytes, int defer_finish, dycon_stream_t stream) {
+    return conv_fwd_launch(x, wfrag, bias, y, dtype, mode, scatter, accumulate, B, Di, Hi, Wi, Cin, N, Cout, workspace, ws_bytes, defer_finish,
+                           nullptr, stream);
+}
 
 extern "C" int dycon_conv_gemm(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int mode,
                                int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout,
                                float* workspace, size_t ws_bytes, dycon_stream_t stream) {
-    return dycon_conv_gemm_ex(x, wfrag, bias, y, dtype, mode, scatter, accumulate, B, Di, Hi, Wi, Cin, N, Cout, workspace, ws_bytes, 0,
-                              stream);
+    return conv_fwd_launch(x, wfrag, bias, y, dtype, mode, scatter, accumulate, B, Di, Hi, Wi, Cin, N, Cout, workspace, ws_bytes, 0, nullptr,
+                           stream);
 }
 
-static thread_local float* g_stat_part = nullptr;      // set by dycon_conv_gemm_stats around its call of dycon_conv_gemm_ex
-
-static bool conv_p32_shape(int dtype, int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
-    const int nTiles = B * cdiv(Di, CL_TZ) * cdiv(Hi, CL_TY) * cdiv(Wi, CL_TX);
-    return dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && !accumulate && Cin == 32 && Cout == 32 &&
-           (long long)Di * Hi * Wi >= 13824 && nTiles >= 1024;
-}
-// rows per sample of the statistics partials a dycon_conv_gemm_stats call of this shape writes (0: shape not served)
-extern "C" int dycon_conv_stats_chunks(int dtype, int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
-    const int nTiles = B * cdiv(Di, CL_TZ) * cdiv(Hi, CL_TY) * cdiv(Wi, CL_TX);
-    // the persistent kernels of the 16-channel level (conv_k3_p16 16 -> 16, conv_k3_c1 1 -> 16): one row per workgroup of their grids
-    if (dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && Cout == 16 && (Cin == 16 || Cin == 1) && (long long)Di * Hi * Wi >= 13824)
-        return 8 * min(cdiv(nTiles, 8), Cin == 16 ? 32 * P16_WGS : 128);
-    if (!conv_p32_shape(dtype, mode, 0, 0, B, Di, Hi, Wi, Cin, Cout)) return 0;
-    return 8 * min(cdiv(nTiles, 8), 32);
-}
-extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int mode,
-                                  int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout,
-                                  float* workspace, size_t ws_bytes, int defer_finish, dycon_stream_t stream);
 // dycon_conv_gemm (k=3, no scatter / accumulation) on a shape dycon_conv_stats_chunks serves, which ALSO leaves per-(sample, chunk,
 // channel) {sum, sum of squares} of the stored outputs in stat_part ([B][chunks][Cout][2] floats): the statistics pass of the
 // normalisation that follows is then dycon_norm_fwd_parts (finalize + apply) instead of a read of the whole tensor.
@@ -3005,120 +3168,7 @@ extern "C" int dycon_conv_gemm_stats(const void* x, const void* wfrag, const flo
     const int chunks = dycon_conv_stats_chunks(dtype, DYCON_CONV_K3, B, Di, Hi, Wi, Cin, Cout);
     DYCON_REQUIRE(chunks > 0, "conv_gemm_stats: shape not served (ask dycon_conv_stats_chunks)");
     DYCON_REQUIRE(stat_part && stat_bytes >= (size_t)B * chunks * Cout * 2 * sizeof(float), "conv_gemm_stats: statistics buffer too small");
-    g_stat_part = stat_part;
-    const int rc = dycon_conv_gemm_ex(x, wfrag, bias, y, dtype, DYCON_CONV_K3, 0, 0, B, Di, Hi, Wi, Cin, Cout, Cout, nullptr, 0, 0, stream);
-    g_stat_part = nullptr;
-    return rc;
-}
-
-extern "C" int dycon_conv_gemm_ex(const void* x, const void* wfrag, const float* bias, void* y, int dtype, int mode,
-                                  int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N, int Cout,
-                                  float* workspace, size_t ws_bytes, int defer_finish, dycon_stream_t stream) {
-    DYCON_REQUIRE(x && wfrag && y, "conv_gemm: null pointer");
-    DYCON_REQUIRE(!defer_finish || (!accumulate && workspace && dycon_conv_gemm_splits(dtype, mode, scatter, B, Di, Hi, Wi, Cin, N) > 1 &&
-                                    ws_bytes >= dycon_conv_gemm_workspace(dtype, mode, scatter, B, Di, Hi, Wi, Cin, N)),
-                  "conv_gemm: defer_finish needs a split-K shape, its workspace and no accumulation");
-    DYCON_REQUIRE(B > 0 && Di > 0 && Hi > 0 && Wi > 0 && Cin > 0 && N > 0 && Cout > 0, "conv_gemm: bad shape");
-    DYCON_REQUIRE(mode >= 0 && mode <= 2, "conv_gemm: bad mode %d", mode);
-    const bool first_layer_lds = dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter && Cin == 1 &&
-                                 (Cout == 16 || Cout == 32 || Cout == 64) && (long long)Di * Hi * Wi >= 13824;
-    DYCON_REQUIRE(first_layer_lds || Cin % (dtype == DYCON_BF16 ? 8 : 4) == 0, "conv_gemm: Cin=%d not a multiple of the fragment width", Cin);
-    DYCON_REQUIRE(N % 16 == 0, "conv_gemm: N=%d not a multiple of 16 (use dycon_conv_direct)", N);
-    DYCON_REQUIRE(!scatter || (mode == DYCON_CONV_1X1 && N == 8 * Cout), "conv_gemm: scatter needs mode 1x1 and N == 8*Cout");
-    DYCON_REQUIRE(scatter || N == Cout, "conv_gemm: N must equal Cout without scatter");
-    DYCON_REQUIRE(mode != DYCON_CONV_K2S2 || (Di % 2 == 0 && Hi % 2 == 0 && Wi % 2 == 0), "conv_gemm: k2s2 needs even dims");
-    // large spatial levels, bf16: LDS-halo kernel
-    if (dtype == DYCON_BF16 && mode == DYCON_CONV_K3 && !scatter &&
-        ((Cin == 1 && (Cout == 16 || Cout == 32 || Cout == 64)) ||
-         ((Cin == 16 || Cin == 48 || Cin % 32 == 0) && (Cout == 16 || Cout == 32 || Cout % 64 == 0 || Cout % 48 == 0))) &&
-        (long long)Di * Hi * Wi >= 13824) {
-        const int tz = cdiv(Di, CL_TZ), ty = cdiv(Hi, CL_TY), tx = cdiv(Wi, CL_TX);
-        const int NT = Cout / 16;
-        const int ntb = Cout % 64 == 0 ? CL_NTB64 : (Cout % 48 == 0 ? 3 : NT);
-        const int nTiles = B * tz * ty * tx;
-        // persistent kernels of the 16-channel level: 8 XCDs x up to 64 (p16: 2 per CU) / 128 (c1) workgroups
-        if ((Cin == 16 && Cout == 16) || (Cin == 1 && (Cout == 16 || Cout == 32 || Cout == 64))) {
-            const int per_xcd = min(cdiv(nTiles, 8), Cin == 16 ? 32 * P16_WGS : 128);
-            const bf16 *xp = (const bf16*)x, *wp = (const bf16*)wfrag;
-            bf16* yp = (bf16*)y;
-            if (Cin == 16 && accumulate) conv_k3_p16_kernel<P16_DEPTH, true><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles);
-            else if (Cin == 16 && g_stat_part) conv_k3_p16_kernel<P16_DEPTH, false, true><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles, g_stat_part);
-            else if (Cin == 16) conv_k3_p16_kernel<P16_DEPTH, false><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles);
-            else if (Cout == 16 && g_stat_part && !accumulate) conv_k3_c1_kernel<1, true><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles, 0, g_stat_part);
-            else if (Cout == 16) conv_k3_c1_kernel<1><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles, accumulate);
-            else if (Cout == 32) conv_k3_c1_kernel<2><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles, accumulate);
-            else conv_k3_c1_kernel<4><<<8 * per_xcd, 256, 0, stream>>>(xp, wp, bias, yp, B, Di, Hi, Wi, tz, ty, tx, nTiles, accumulate);
-            DYCON_LAUNCH_CHECK();
-            return DYCON_OK;
-        }
-        // 32 -> 32 with several tiles per CU: persistent kernel, weights stationary in LDS (one workgroup per CU)
-        // (a 32x32x16 MFMA form measured slower, 30.9 against 28.5 us per launch at 48^3, and was removed: DESIGN section 9)
-        if (Cin == 32 && Cout == 32 && !accumulate && nTiles >= 1024) {
-            const int per_xcd = min(cdiv(nTiles, 8), 32);
-#define DYCON_P32(STV) conv_k3_p32_kernel<8, STV><<<8 * per_xcd, 64 * 8, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, tz, ty, tx, nTiles, g_stat_part)
-            if (g_stat_part) DYCON_P32(true); else DYCON_P32(false);
-#undef DYCON_P32
-            DYCON_LAUNCH_CHECK();
-            return DYCON_OK;
-        }
-        dim3 grid(nTiles, NT / ntb);
-#define DYCON_CL(CKV, NTBV, WMV) \
-    conv_k3_lds_kernel<CKV, NTBV, WMV><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, Cin, Cout, NT, tz, ty, tx, accumulate)
-        if (Cin == 16 || Cin == 48) {
-            if (ntb == 1) DYCON_CL(16, 1, 4); else if (ntb == 2) DYCON_CL(16, 2, 4); else if (ntb == 3) DYCON_CL(16, 3, 4); else DYCON_CL(16, 4, 2);
-        } else {
-            if (ntb == 1) DYCON_CL(32, 1, 4); else if (ntb == 2) DYCON_CL(32, 2, 4); else if (ntb == 3) DYCON_CL(32, 3, 4);
-            else if ((long long)nTiles * (NT / ntb) <= 256)     // at most one workgroup per CU: 8 waves, two per SIMD (a wave per SIMD is issue-bound)
-                conv_k3_lds_kernel<32, 4, 4, 8><<<grid, 512, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, B, Di, Hi, Wi, Cin, Cout, NT, tz, ty, tx, accumulate);
-            else DYCON_CL(32, 4, 2);
-        }
-#undef DYCON_CL
-        DYCON_LAUNCH_CHECK();
-        return DYCON_OK;
-    }
-    if (conv_halo_ok(dtype, mode, scatter, (long long)B * Di * Hi * Wi, (long long)Di * Hi * Wi, Cin, N)) {
-        const long long M = (long long)B * Di * Hi * Wi;
-        const int tz = cdiv(Di, CH_T), ty = cdiv(Hi, CH_T), tx = cdiv(Wi, CH_T);
-        const SplitK sk = conv_tile_plan(M, N, Cin);
-        const dim3 grid(B * tz * ty * tx, N / 64);
-#define DYCON_CH(NJV) conv_k3_halo_kernel<NJV><<<grid, 64 * CH_NW, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, Di, Hi, Wi, N, N / 16, tz, ty, tx, sk.splits, sk.kc_per_split, accumulate)
-        if (sk.splits > 2) DYCON_CH(2); else DYCON_CH(1);
-#undef DYCON_CH
-        DYCON_LAUNCH_CHECK();
-        return DYCON_OK;
-    }
-    if (conv_tile_ok(dtype, mode, scatter, (long long)Di * Hi * Wi, Cin, N)) {
-        const long long M = (long long)B * Di * Hi * Wi;
-        const int NT = N / 16, nKC = 27 * Cin / 32;
-        SplitK sk = conv_tile_plan(M, N, Cin);
-        const bool split = sk.splits > 1 && workspace && ws_bytes >= (size_t)sk.splits * M * N * sizeof(float);
-        dim3 grid(cdiv(M, CT_BM), N / CT_BN, split ? sk.splits : 1);
-        const int layout = split && defer_finish ? 1 : 0;
-        if (Cin % 64 == 0 && sk.kc_per_split % 2 == 0)
-            conv_k3_tile_kernel<2><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, split ? workspace : nullptr, B,
-                                                             Di, Hi, Wi, Cin, N, NT, nKC, sk.kc_per_split, accumulate, layout);
-        else
-            conv_k3_tile_kernel<1><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)wfrag, bias, (bf16*)y, split ? workspace : nullptr, B,
-                                                             Di, Hi, Wi, Cin, N, NT, nKC, sk.kc_per_split, accumulate, layout);
-        DYCON_LAUNCH_CHECK();
-        if (split && !defer_finish) {
-            long long blocks = (M * N / 4 + 255) / 256;
-            if (blocks > 2048) blocks = 2048;
-            splitk_finish_kernel<bf16><<<(int)blocks, 256, 0, stream>>>(workspace, sk.splits, M * N, N, bias, (bf16*)y, accumulate);
-            DYCON_LAUNCH_CHECK();
-        }
-        return DYCON_OK;
-    }
-    // split-K only when the caller provides the slab workspace (NULL -> single pass, same result up to fp32 summation order)
-    float* ws = (workspace && ws_bytes >= dycon_conv_gemm_workspace(dtype, mode, scatter, B, Di, Hi, Wi, Cin, N)) ? workspace : nullptr;
-    DYCON_DISPATCH(dtype, {
-        if (scatter) launch_gemm<T, DYCON_CONV_1X1, true>(x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, ws, defer_finish, stream);
-        else if (mode == DYCON_CONV_K3) launch_gemm<T, DYCON_CONV_K3, false>(x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, ws, defer_finish, stream);
-        else if (mode == DYCON_CONV_K2S2) launch_gemm<T, DYCON_CONV_K2S2, false>(x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, ws, defer_finish, stream);
-        else launch_gemm<T, DYCON_CONV_1X1, false>(x, wfrag, bias, y, accumulate, B, Di, Hi, Wi, Cin, N, Cout, ws, defer_finish, stream);
-    });
-    DYCON_LAUNCH_CHECK();
-    return DYCON_OK;
+    return conv_fwd_launch(x, wfrag, bias, y, dtype, DYCON_CONV_K3, 0, 0, B, Di, Hi, Wi, Cin, Cout, Cout, nullptr, 0, 0, stat_part, stream);
 }
 
 template <typename TI, typename TO>
@@ -3168,95 +3218,33 @@ extern "C" int dycon_conv_direct(const void* x, int x_dtype, const float* w_tcn,
     return DYCON_OK;
 }
 
-// ---- weight gradient planning (shared by the workspace query and the launch)
-struct WgradPlan { bool mfma; int splits; long long rows_per_split; int L; };
-static WgradPlan wgrad_plan(int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
-    int Do, Ho, Wo;
-    row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
-    const long long M = (long long)B * Do * Ho * Wo;
-    const int Tn = mode == DYCON_CONV_K3 ? 27 : mode == DYCON_CONV_K2S2 ? 8 : 1;
-    WgradPlan p;
-    p.L = Tn * Cin * Cout;
-    p.mfma = (Cin % 16 == 0) && (Cout % 16 == 0);
-    if (p.mfma) {
-        const long long blocks_xy = (long long)(Cin / 16) * cdiv(Cout, 16 * NTB) * Tn;
-        long long want = (2048 + blocks_xy - 1) / blocks_xy;           // aim for ~2k workgroups
-        long long max_by_rows = (M + 255) / 256;                       // >= 256 rows per split
-        long long s = want < 1 ? 1 : want;
-        if (s > max_by_rows) s = max_by_rows;
-        if (s > 256) s = 256;
-        if (s < 1) s = 1;
-        long long rps = (M + s - 1) / s;
-        rps = (rps + 15) / 16 * 16;
-        p.splits = (int)((M + rps - 1) / rps);
-        p.rows_per_split = rps;
-    } else {
-        long long rps = 1024;
-        p.splits = (int)((M + rps - 1) / rps);
-        p.rows_per_split = rps;
-    }
-    return p;
-}
-
 extern "C" size_t dycon_colsum_workspace(long long rows, int C);
 extern "C" int dycon_colsum(const void* x, int dtype, float* out, long long rows, int C, float* workspace, size_t ws_bytes,
                             dycon_stream_t stream);
 
-// k=3 bf16 plan: tiles and voxel-tile splits
-struct WgradK3Plan { int tilesZ, tilesY, tilesX, nTiles, gx, nCoBlk, NT, splits; };
-static WgradK3Plan wgrad_k3_plan(int B, int D, int H, int W, int Cin, int Cout) {
-    WgradK3Plan p;
+// tiles and voxel-tile splits of the bf16 tile kernels (k3, k2s2, 1x1)
+struct WgradTiles { int tilesZ, tilesY, tilesX, nTiles, gx, nCoBlk, NT, splits; };
+// k3: tiles over the grid, partial slabs capped at ~24 MB (fewer splits = fewer workgroups = slower: measured); k2s2: tiles over the
+// LO (half) grid D x H x W, 16 MB
+static WgradTiles wgrad_tile_plan(int B, int D, int H, int W, int Cin, int Cout, int taps, long long slab_mb) {
+    WgradTiles p;
     p.tilesZ = cdiv(D, WG_TZ); p.tilesY = cdiv(H, WG_TY); p.tilesX = cdiv(W, WG_TX);
     p.nTiles = B * p.tilesZ * p.tilesY * p.tilesX;
     p.NT = Cout >= 64 ? 4 : Cout / 16;
     p.nCoBlk = cdiv(Cout, 16 * p.NT);
     p.gx = ((Cin + 15) / 16) * p.nCoBlk;
-    const long long L = 27LL * Cin * Cout;
-    long long s = 2048 / p.gx;
-    constexpr long long slab_mb = 24;
-    const long long cap = (slab_mb << 20) / (4 * L) > 0 ? (slab_mb << 20) / (4 * L) : 1;   // partial slabs capped at ~24 MB (fewer splits = fewer workgroups = slower: measured)
-    if (s > cap) s = cap;
-    if (s > p.nTiles) s = p.nTiles;
-    if (s < 1) s = 1;
-    p.splits = (int)s;
+    const long long cap = (slab_mb << 20) / (4LL * taps * Cin * Cout);
+    p.splits = (int)max(1LL, min(min(2048LL / p.gx, cap), (long long)p.nTiles));
     return p;
 }
-static bool wgrad_k2_ok(int mode, int Cin, int Cout) {
-    return mode == DYCON_CONV_K2S2 && Cin % 16 == 0 && Cout % 16 == 0 && (Cout == 16 || Cout == 32 || Cout % 64 == 0);
-}
-static WgradK3Plan wgrad_k2_plan(int B, int Di, int Hi, int Wi, int Cin, int Cout) {   // tiles over the LO (half) grid
-    WgradK3Plan p;
-    p.tilesZ = cdiv(Di / 2, WG_TZ); p.tilesY = cdiv(Hi / 2, WG_TY); p.tilesX = cdiv(Wi / 2, WG_TX);
-    p.nTiles = B * p.tilesZ * p.tilesY * p.tilesX;
-    p.NT = Cout >= 64 ? 4 : Cout / 16;
-    p.nCoBlk = cdiv(Cout, 16 * p.NT);
-    p.gx = (Cin / 16) * p.nCoBlk;
-    const long long L = 8LL * Cin * Cout;
-    long long s = 2048 / p.gx;
-    const long long cap = (16LL << 20) / (4 * L);
-    if (s > cap) s = cap;
-    if (s > p.nTiles) s = p.nTiles;
-    if (s < 1) s = 1;
-    p.splits = (int)s;
-    return p;
-}
-static bool wgrad_1x1_ok(int mode, int Cin, int Cout) {
-    return mode == DYCON_CONV_1X1 && Cin % W1_CI == 0 && Cout % 16 == 0 && (Cout == 16 || Cout == 32 || Cout % 64 == 0);
-}
-static WgradK3Plan wgrad_1x1_plan(long long M, int Cin, int Cout) {
-    WgradK3Plan p{};
+static WgradTiles wgrad_1x1_plan(long long M, int Cin, int Cout) {
+    WgradTiles p{};
     p.nTiles = (int)((M + W1_ROWS - 1) / W1_ROWS);
     p.NT = Cout >= 64 ? 4 : Cout / 16;
     p.nCoBlk = cdiv(Cout, 16 * p.NT);
     p.gx = (Cin / W1_CI) * p.nCoBlk;
-    long long s_ = 512 / p.gx;
-    if (s_ > p.nTiles) s_ = p.nTiles;
-    if (s_ < 1) s_ = 1;
-    p.splits = (int)s_;
+    p.splits = max(1, min(512 / p.gx, p.nTiles));
     return p;
-}
-static bool wgrad_k3_ok(int mode, int Cin, int Cout) {
-    return mode == DYCON_CONV_K3 && (Cin % 16 == 0 || Cin == 1) && Cout % 16 == 0 && (Cout == 16 || Cout == 32 || Cout % 64 == 0);
 }
 
 static int wgrad_c1_wgs(int B, int Di, int Hi, int Wi) {      // persistent workgroups (= partial rows) of wgrad_k3_c1_kernel
@@ -3293,25 +3281,76 @@ extern "C" int dycon_conv1_wgrad_normbwd(const void* x, const void* z, const voi
 }
 
 
-extern "C" size_t dycon_conv_wgrad_workspace(int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
-    const WgradPlan p = wgrad_plan(mode, B, Di, Hi, Wi, Cin, Cout);
-    size_t need = (size_t)p.splits * p.L * sizeof(float);
-    if (mode == DYCON_CONV_K3 && Cin == 1 && Cout == 16) {
-        const size_t n3 = (size_t)wgrad_c1_wgs(B, Di, Hi, Wi) * (p.L + Cout) * sizeof(float);
-        if (n3 > need) need = n3;
+// ---- the weight-gradient plan (the workspace query, the launch and the name query read it): family, tiles, partial rows
+enum { WG_C1, WG_K3, WG_K2S2, WG_1X1, WG_SKINNY, WG_MFMA, WG_DIRECT };      // WG_C1 .. WG_1X1: bf16 tile kernels, bias gradient fused
+struct WgradPlan {
+    int family;
+    int L;                      // elements of dw
+    int rows;                   // partial rows the launch leaves for the reduce
+    long long rows_per_split;   // generic kernels: voxel rows per partial row
+    WgradTiles k;               // tile kernels: grid (k.gx, k.splits)
+};
+// the generic kernels (any dtypes): MFMA when both channel counts fill 16-wide fragments, else direct; one partial row per split
+static WgradPlan wgrad_generic_plan(int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
+    int Do, Ho, Wo;
+    row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
+    const long long M = (long long)B * Do * Ho * Wo;
+    const int Tn = mode == DYCON_CONV_K3 ? 27 : mode == DYCON_CONV_K2S2 ? 8 : 1;
+    WgradPlan p{};
+    p.L = Tn * Cin * Cout;
+    p.family = (Cin % 16 == 0 && Cout % 16 == 0) ? WG_MFMA : WG_DIRECT;
+    if (p.family == WG_MFMA) {
+        const long long blocks_xy = (long long)(Cin / 16) * cdiv(Cout, 16 * NTB) * Tn;
+        // aim for ~2k workgroups, >= 256 rows per split, at most 256 splits
+        const long long s = max(1LL, min(min((2048 + blocks_xy - 1) / blocks_xy, (M + 255) / 256), 256LL));
+        long long rps = (M + s - 1) / s;
+        p.rows_per_split = (rps + 15) / 16 * 16;
+    } else {
+        p.rows_per_split = 1024;
     }
-    if (wgrad_k3_ok(mode, Cin, Cout) || wgrad_k2_ok(mode, Cin, Cout)) {
-        const WgradK3Plan k = mode == DYCON_CONV_K3 ? wgrad_k3_plan(B, Di, Hi, Wi, Cin, Cout) : wgrad_k2_plan(B, Di, Hi, Wi, Cin, Cout);
-        const size_t n2 = ((size_t)k.splits * p.L + (size_t)k.splits * Cout) * sizeof(float);
+    p.rows = (int)((M + p.rows_per_split - 1) / p.rows_per_split);
+    return p;
+}
+static WgradPlan wgrad_plan(int x_dtype, int g_dtype, int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
+    WgradPlan p = wgrad_generic_plan(mode, B, Di, Hi, Wi, Cin, Cout);
+    if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16 && (Cout == 16 || Cout == 32 || Cout % 64 == 0)) {
+        if (mode == DYCON_CONV_K3 && (Cin % 16 == 0 || Cin == 1)) {
+            p.k = wgrad_tile_plan(B, Di, Hi, Wi, Cin, Cout, 27, 24);
+            // first layer: transposed product, persistent workgroups (wgrad_k3_c1_kernel)
+            p.family = (Cin == 1 && Cout == 16) ? WG_C1 : WG_K3;
+        } else if (mode == DYCON_CONV_K2S2 && Cin % 16 == 0) {
+            p.k = wgrad_tile_plan(B, Di / 2, Hi / 2, Wi / 2, Cin, Cout, 8, 16);
+            p.family = WG_K2S2;
+        } else if (mode == DYCON_CONV_1X1 && Cin % W1_CI == 0) {
+            p.k = wgrad_1x1_plan((long long)B * Di * Hi * Wi, Cin, Cout);
+            p.family = WG_1X1;
+        }
+        if (p.family <= WG_1X1) p.rows = p.family == WG_C1 ? wgrad_c1_wgs(B, Di, Hi, Wi) : p.k.splits;
+    } else if (mode == DYCON_CONV_1X1 && Cin == 16 && Cout == 2 && g_dtype == DYCON_F32) {     // the 2-class head: at most 1024 rows
+        p.family = WG_SKINNY;
+        if (p.rows > 1024) p.rows = 1024;
+    }
+    return p;
+}
+
+extern "C" const char* dycon_conv_wgrad_name(int x_dtype, int g_dtype, int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
+    static const char* const names[] = {"wgrad_k3_c1", "wgrad_k3_bf16", "wgrad_k2s2_bf16", "wgrad_1x1_bf16", "wgrad_1x1_skinny", "conv_wgrad",
+                                        "conv_wgrad_direct"};
+    return names[wgrad_plan(x_dtype, g_dtype, mode, B, Di, Hi, Wi, Cin, Cout).family];
+}
+
+// no dtype arguments: the largest need over the families the shape can take (the generic kernels' rows; the tile kernels' rows with a
+// bias row each -- for the first layer the larger of its persistent grid and the k3 tile plan, as this query has always answered)
+extern "C" size_t dycon_conv_wgrad_workspace(int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout) {
+    const WgradPlan g = wgrad_generic_plan(mode, B, Di, Hi, Wi, Cin, Cout);
+    const WgradPlan t = wgrad_plan(DYCON_BF16, DYCON_BF16, mode, B, Di, Hi, Wi, Cin, Cout);
+    size_t need = (size_t)g.rows * g.L * sizeof(float);
+    if (t.family <= WG_1X1) {
+        const size_t n2 = (size_t)max(t.rows, t.k.splits) * (t.L + Cout) * sizeof(float);
         if (n2 > need) need = n2;
     }
     int Do, Ho, Wo;
     row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
-    if (wgrad_1x1_ok(mode, Cin, Cout)) {
-        const WgradK3Plan k = wgrad_1x1_plan((long long)B * Di * Hi * Wi, Cin, Cout);
-        const size_t n2 = ((size_t)k.splits * p.L + (size_t)k.splits * Cout) * sizeof(float);
-        if (n2 > need) need = n2;
-    }
     return need + dycon_colsum_workspace((long long)B * Do * Ho * Wo, Cout) + 64;   // room for the un-fused bias gradient
 }
 
@@ -3348,9 +3387,9 @@ static void launch_wgrad(const void* x, const void* gy, float* part, int mode, c
     int Do, Ho, Wo;
     row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
     const int Tn = mode == DYCON_CONV_K3 ? 27 : mode == DYCON_CONV_K2S2 ? 8 : 1;
-    if (p.mfma) {
+    if (p.family == WG_MFMA) {
         const int nCoBlk = cdiv(Cout, 16 * NTB);
-        dim3 grid((Cin / 16) * nCoBlk, Tn, p.splits);
+        dim3 grid((Cin / 16) * nCoBlk, Tn, p.rows);
 #define DYCON_WG(MODE) \
     conv_wgrad_kernel<TX, TG, MODE><<<grid, 256, 0, stream>>>((const TX*)x, (const TG*)gy, part, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, nCoBlk, p.rows_per_split)
         if (mode == DYCON_CONV_K3) DYCON_WG(DYCON_CONV_K3);
@@ -3358,7 +3397,7 @@ static void launch_wgrad(const void* x, const void* gy, float* part, int mode, c
         else DYCON_WG(DYCON_CONV_1X1);
 #undef DYCON_WG
     } else {
-        dim3 grid(p.splits, cdiv(p.L, 256));
+        dim3 grid(p.rows, cdiv(p.L, 256));
 #define DYCON_WGD(MODE) \
     conv_wgrad_direct_kernel<TX, TG, MODE><<<grid, 256, 0, stream>>>((const TX*)x, (const TG*)gy, part, B, Di, Hi, Wi, Cin, Do, Ho, Wo, Cout, p.rows_per_split)
         if (mode == DYCON_CONV_K3) DYCON_WGD(DYCON_CONV_K3);
@@ -3375,96 +3414,64 @@ extern "C" int dycon_conv_wgrad(const void* x, int x_dtype, const void* gy, int 
     DYCON_REQUIRE(B > 0 && Di > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Cout > 0, "conv_wgrad: bad shape");
     DYCON_REQUIRE(mode >= 0 && mode <= 2, "conv_wgrad: bad mode %d", mode);
     DYCON_REQUIRE(ws_bytes >= dycon_conv_wgrad_workspace(mode, B, Di, Hi, Wi, Cin, Cout), "conv_wgrad: workspace too small");
-    const WgradPlan p = wgrad_plan(mode, B, Di, Hi, Wi, Cin, Cout);
-    if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16 && wgrad_k3_ok(mode, Cin, Cout)) {
-        const WgradK3Plan k = wgrad_k3_plan(B, Di, Hi, Wi, Cin, Cout);
-        if (Cin == 1 && Cout == 16) {      // first layer: transposed product, persistent workgroups (wgrad_k3_c1_kernel)
-            const int tz = cdiv(Di, CL_TZ), ty = cdiv(Hi, CL_TY), tx = cdiv(Wi, CL_TX);
-            const int nTiles = B * tz * ty * tx;
-            const int wgs = wgrad_c1_wgs(B, Di, Hi, Wi);
-            float* bp = dbias ? workspace + (size_t)wgs * p.L : nullptr;
-            wgrad_k3_c1_kernel<false><<<wgs, 256, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bp, B, Di, Hi, Wi, tz, ty, tx, nTiles, C1NormBwd{});
-            DYCON_LAUNCH_CHECK();
-            launch_reduce_partials(workspace, wgs, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream, bp, dbias);
-            DYCON_LAUNCH_CHECK();
-            return DYCON_OK;
-        }
-        float* bpart = dbias ? workspace + (size_t)k.splits * p.L : nullptr;
-        dim3 grid(k.gx, k.splits);
+    DYCON_REQUIRE((x_dtype == DYCON_F32 || x_dtype == DYCON_BF16) && (g_dtype == DYCON_F32 || g_dtype == DYCON_BF16), "conv_wgrad: bad dtypes");
+    const WgradPlan p = wgrad_plan(x_dtype, g_dtype, mode, B, Di, Hi, Wi, Cin, Cout);
+    const WgradTiles& k = p.k;
+    const bool tiled = p.family <= WG_1X1;                     // weights + bias: one kernel, one reduce launch
+    float* bpart = tiled && dbias ? workspace + (size_t)p.rows * p.L : nullptr;
+    const dim3 grid(k.gx, k.splits);
+    const bf16 *xp = (const bf16*)x, *gp = (const bf16*)gy;
+    const long long M = (long long)B * Di * Hi * Wi;
+    switch (p.family) {
+    case WG_C1: {
+        const int tz = cdiv(Di, CL_TZ), ty = cdiv(Hi, CL_TY), tx = cdiv(Wi, CL_TX);
+        wgrad_k3_c1_kernel<false><<<p.rows, 256, 0, stream>>>(xp, gp, workspace, bpart, B, Di, Hi, Wi, tz, ty, tx, B * tz * ty * tx, C1NormBwd{});
+        break;
+    }
+    case WG_K3:
 #define DYCON_WK3(NTV, C1) \
-    wgrad_k3_bf16_kernel<NTV, C1><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX)
+    wgrad_k3_bf16_kernel<NTV, C1><<<grid, 256, 0, stream>>>(xp, gp, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX)
         if (Cin != 1 && k.NT == 4 && (long long)k.gx * k.splits <= 256)      // at most one workgroup per CU: 8 waves, two per SIMD
-            wgrad_k3_bf16_kernel<4, false, 8><<<grid, 512, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX);
+            wgrad_k3_bf16_kernel<4, false, 8><<<grid, 512, 0, stream>>>(xp, gp, workspace, bpart, B, Di, Hi, Wi, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX);
         else if (Cin == 1) { if (k.NT == 1) DYCON_WK3(1, true); else if (k.NT == 2) DYCON_WK3(2, true); else DYCON_WK3(4, true); }
         else if (k.NT == 1) DYCON_WK3(1, false);
         else if (k.NT == 2) DYCON_WK3(2, false);
         else DYCON_WK3(4, false);
 #undef DYCON_WK3
-        DYCON_LAUNCH_CHECK();
-        launch_reduce_partials(workspace, k.splits, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream, bpart, dbias);   // weights + bias: one launch
-        DYCON_LAUNCH_CHECK();
-        return DYCON_OK;
-    }
-    if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16 && wgrad_k2_ok(mode, Cin, Cout)) {
-        const WgradK3Plan k = wgrad_k2_plan(B, Di, Hi, Wi, Cin, Cout);
-        float* bpart = dbias ? workspace + (size_t)k.splits * p.L : nullptr;
-        dim3 grid(k.gx, k.splits);
+        break;
+    case WG_K2S2:
 #define DYCON_WK2(NTV) \
-    wgrad_k2s2_bf16_kernel<NTV><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, B, Di / 2, Hi / 2, Wi / 2, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX)
+    wgrad_k2s2_bf16_kernel<NTV><<<grid, 256, 0, stream>>>(xp, gp, workspace, bpart, B, Di / 2, Hi / 2, Wi / 2, Cin, Cout, k.nCoBlk, k.nTiles, k.tilesZ, k.tilesY, k.tilesX)
         if (k.NT == 1) DYCON_WK2(1);
         else if (k.NT == 2) DYCON_WK2(2);
         else DYCON_WK2(4);
 #undef DYCON_WK2
-        DYCON_LAUNCH_CHECK();
-        launch_reduce_partials(workspace, k.splits, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream, bpart, dbias);   // weights + bias: one launch
-        DYCON_LAUNCH_CHECK();
-        return DYCON_OK;
-    }
-    if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16 && wgrad_1x1_ok(mode, Cin, Cout)) {
-        const long long M = (long long)B * Di * Hi * Wi;
-        const WgradK3Plan k = wgrad_1x1_plan(M, Cin, Cout);
-        float* bpart = dbias ? workspace + (size_t)k.splits * p.L : nullptr;
-        dim3 grid(k.gx, k.splits);
-#define DYCON_W11(NTV) \
-    wgrad_1x1_bf16_kernel<NTV><<<grid, 256, 0, stream>>>((const bf16*)x, (const bf16*)gy, workspace, bpart, M, Cin, Cout, k.nCoBlk, k.nTiles)
+        break;
+    case WG_1X1:
+#define DYCON_W11(NTV) wgrad_1x1_bf16_kernel<NTV><<<grid, 256, 0, stream>>>(xp, gp, workspace, bpart, M, Cin, Cout, k.nCoBlk, k.nTiles)
         if (k.NT == 1) DYCON_W11(1);
         else if (k.NT == 2) DYCON_W11(2);
         else DYCON_W11(4);
 #undef DYCON_W11
-        DYCON_LAUNCH_CHECK();
-        launch_reduce_partials(workspace, k.splits, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream, bpart, dbias);
-        DYCON_LAUNCH_CHECK();
-        return DYCON_OK;
+        break;
+    case WG_SKINNY:
+        if (x_dtype == DYCON_F32) wgrad_1x1_skinny_kernel<float, float, 16, 2><<<p.rows, 256, 0, stream>>>((const float*)x, (const float*)gy, workspace, M);
+        else wgrad_1x1_skinny_kernel<bf16, float, 16, 2><<<p.rows, 256, 0, stream>>>(xp, (const float*)gy, workspace, M);
+        break;
+    default:
+        if (x_dtype == DYCON_F32 && g_dtype == DYCON_F32) launch_wgrad<float, float>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
+        else if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16) launch_wgrad<bf16, bf16>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
+        else if (x_dtype == DYCON_BF16 && g_dtype == DYCON_F32) launch_wgrad<bf16, float>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
+        else launch_wgrad<float, bf16>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
     }
-    if (mode == DYCON_CONV_1X1 && Cin == 16 && Cout == 2 && g_dtype == DYCON_F32) {
-        const long long M = (long long)B * Di * Hi * Wi;
-        int blocks = p.splits;                      // partial rows available in the workspace (>= M/1024)
-        if (blocks > 1024) blocks = 1024;
-        if (x_dtype == DYCON_F32) wgrad_1x1_skinny_kernel<float, float, 16, 2><<<blocks, 256, 0, stream>>>((const float*)x, (const float*)gy, workspace, M);
-        else wgrad_1x1_skinny_kernel<bf16, float, 16, 2><<<blocks, 256, 0, stream>>>((const bf16*)x, (const float*)gy, workspace, M);
-        DYCON_LAUNCH_CHECK();
-        launch_reduce_partials(workspace, blocks, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream);
-        DYCON_LAUNCH_CHECK();
-        if (dbias) {
-            float* cws = workspace + (size_t)p.splits * p.L;
-            return dycon_colsum(gy, g_dtype, dbias, M, Cout, cws, dycon_colsum_workspace(M, Cout), stream);
-        }
-        return DYCON_OK;
-    }
-    if (x_dtype == DYCON_F32 && g_dtype == DYCON_F32) launch_wgrad<float, float>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
-    else if (x_dtype == DYCON_BF16 && g_dtype == DYCON_BF16) launch_wgrad<bf16, bf16>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
-    else if (x_dtype == DYCON_BF16 && g_dtype == DYCON_F32) launch_wgrad<bf16, float>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
-    else if (x_dtype == DYCON_F32 && g_dtype == DYCON_BF16) launch_wgrad<float, bf16>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);
-    else { dycon_set_error("conv_wgrad: bad dtypes"); return DYCON_ERR_INVALID; }
     DYCON_LAUNCH_CHECK();
-    launch_reduce_partials(workspace, p.splits, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream);
+    launch_reduce_partials(workspace, p.rows, p.L, dw, Cin, Cout, s_t, s_c, s_n, stream, bpart, bpart ? dbias : nullptr);
     DYCON_LAUNCH_CHECK();
-    if (dbias) {   // un-fused bias gradient: column sums of gy, partials behind the weight partials
+    if (dbias && !tiled) {   // un-fused bias gradient: column sums of gy, partials behind the weight partials
         int Do, Ho, Wo;
         row_grid(mode, Di, Hi, Wi, Do, Ho, Wo);
         const long long rows = (long long)B * Do * Ho * Wo;
-        float* cws = workspace + (size_t)p.splits * p.L;
-        return dycon_colsum(gy, g_dtype, dbias, rows, Cout, cws, dycon_colsum_workspace(rows, Cout), stream);
+        return dycon_colsum(gy, g_dtype, dbias, rows, Cout, workspace + (size_t)p.rows * p.L, dycon_colsum_workspace(rows, Cout), stream);
     }
     return DYCON_OK;
 }

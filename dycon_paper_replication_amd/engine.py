@@ -17,7 +17,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-from ._lib import CONV_1X1, CONV_K2S2, CONV_K3
+from ._lib import CONV_1X1, CONV_C1, CONV_K2S2, CONV_K3, CONV_W_CHUNK16
 
 UNET_FILTERS = (16, 32, 64, 128, 256)
 VNET_NORMS = ("groupnorm", "instancenorm", "batchnorm", "none")      # VNet.py:17-24
@@ -377,13 +377,13 @@ class Engine:
         gq = 8 if dtype == torch.bfloat16 else 4
         skinny = (Cin % gq != 0) or (Cout % 16 != 0)
         out_dtype = out_dtype or dtype
-        first_lds = (kind == "k3" and Cin == 1 and dtype == torch.bfloat16 and Cout in (16, 32, 64) and out_dtype == dtype
-                     and x.shape[1] * x.shape[2] * x.shape[3] >= 13824)
+        plan = ops.conv_plan_for(x, mode, Cout, Cout) if kind == "k3" and out_dtype == dtype else None
+        first_lds = plan is not None and plan.family == CONV_C1
 
         def conv_with_stats(wf, want):
             """the persistent kernel also takes the statistics of its output (the norm that follows skips its statistics pass);
             None where that is not wanted or the library does not serve the shape"""
-            chunks = ops.conv_stats_chunks(x, Cin, Cout) if (norm_groups and want) else 0
+            chunks = plan.chunks if (norm_groups and want) else 0
             if not chunks:
                 return None
             y, part = ops.conv_gemm_stats(x, wf, b, Cout, chunks)
@@ -402,7 +402,7 @@ class Engine:
         elif kind == "deconv":
             wf = self._pk((name, "f"), "frag", w, 1, Cin, 8 * Cout, Cout, 0, Cout * 8, 1, 8)
             y = ops.conv_gemm(x, wf, b, CONV_1X1, 8 * Cout, Cout, scatter=True)
-        elif kind == "k3" and Cin == 48 and ops.conv_uses_lds(x, Cin, Cout):
+        elif plan is not None and plan.weights == CONV_W_CHUNK16:
             wf = self._pk_chunked16((name, "f48"), w, 3, Cout, 1, 27, Cin * 27)
             y = ops.conv_gemm(x, wf, b, mode, Cout, Cout)
         else:
@@ -463,7 +463,7 @@ class Engine:
                     wd = self._pk((name, "tcn_d"), "tcn", w, 1, Cout, Cin, Cin, 0, Cin, 0, 1)
                     gx = ops.conv_direct(gy, wd, None, CONV_1X1, Cin, x.dtype, out=cur, accumulate=cur is not None)
                 elif kind == "k3":     # conv with flipped taps and transposed channels
-                    if Cout == 48 and ops.conv_uses_lds(gy, Cout, Cin):
+                    if ops.conv_plan_for(gy, CONV_K3, Cin, Cin).weights == CONV_W_CHUNK16:
                         wd = self._pk_chunked16((name, "d48"), w, 3, Cin, 1, Cin * 27, 27, flip=True)
                     else:
                         wd = self._pk((name, "d"), "frag", w, 27, Cout, Cin, Cin, 1, Cin * 27, 0, 27, flip=True)

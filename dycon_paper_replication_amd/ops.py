@@ -6,6 +6,9 @@ PyTorch is used for device memory and streams only -- no torch math runs here.
 """
 from __future__ import annotations
 
+import collections
+import ctypes
+import functools
 from typing import Optional
 
 import torch
@@ -255,14 +258,25 @@ def pack_batch(jobs_dev, njobs, blocks_per_job=8):
     call("dycon_pack_batch", _p(jobs_dev), njobs, blocks_per_job, _s())
 
 
-def conv_uses_lds(x, Cin, Cout):
-    """True when dycon_conv_gemm routes a k=3 conv of this shape to the LDS-halo kernel (bf16, >= 24^3 voxels)."""
-    _, D, H, W, _ = x.shape
-    if x.dtype != torch.bfloat16 or D * H * W < 13824:
-        return False
-    if Cin == 1:
-        return Cout in (16, 32, 64)
-    return (Cin in (16, 48) or Cin % 32 == 0) and (Cout in (16, 32) or Cout % 64 == 0 or Cout % 48 == 0)
+ConvPlan = collections.namedtuple("ConvPlan", "family splits chunks weights workspace name")      # dycon_conv_plan_t + the region name
+
+
+@functools.lru_cache(maxsize=None)
+def conv_plan(dtype, mode, scatter, accumulate, B, D, H, W, Cin, N, Cout):
+    """The library's forward-convolution plan for this shape (dycon_conv_gemm_plan; dtype / mode are the C ABI's integer codes):
+    kernel family (_lib.CONV_*), split-K slabs, workspace bytes, statistics chunks, weight packing (_lib.CONV_W_*) and the kernel's
+    name (the profiler's region name).  Pure host code, one library call per distinct shape."""
+    lib, p = _lib.load(), _lib.ConvPlan()
+    rc = lib.dycon_conv_gemm_plan(dtype, mode, scatter, accumulate, B, D, H, W, Cin, N, Cout, ctypes.byref(p))
+    if rc:
+        raise _lib.DyconLibraryError(f"dycon_conv_gemm_plan failed ({rc}): {lib.dycon_last_error().decode()}")
+    return ConvPlan(p.family, p.splits, p.chunks, p.weights, p.workspace, lib.dycon_conv_region_name(ctypes.byref(p)).decode())
+
+
+def conv_plan_for(x, mode, N, Cout, scatter=False, accumulate=False):
+    """conv_plan of the dycon_conv_gemm call that takes the NDHWC tensor x"""
+    B, D, H, W, Cin = x.shape
+    return conv_plan(dt(x), mode, int(scatter), int(accumulate), B, D, H, W, Cin, N, Cout)
 
 
 # ------------------------------------------------------------------ conv family
@@ -274,23 +288,17 @@ class DeferredConv:
         self.ws, self.splits, self.bias = ws, splits, bias
 
 
+_TAPS = {CONV_K3: 27, CONV_K2S2: 8, CONV_1X1: 1}
+
+
 def conv_gemm(x, wfrag, bias, mode, N, Cout, scatter=False, out=None, accumulate=False, defer_finish=False):
     """defer_finish: on split-K shapes return (out, DeferredConv): `out` is allocated but NOT written; norm_fwd_slab completes it."""
     B, D, H, W, Cin = x.shape
+    plan = conv_plan_for(x, mode, N, Cout, scatter, accumulate)
     if defer_finish:
         assert out is None and not accumulate and not scatter
-        splits = query("dycon_conv_gemm_splits", dt(x), mode, 0, B, D, H, W, Cin, N)
-        if splits <= 1:
+        if plan.splits <= 1:
             return conv_gemm(x, wfrag, bias, mode, N, Cout), None
-        shape = (B, D // 2, H // 2, W // 2, N) if mode == CONV_K2S2 else (B, D, H, W, N)
-        out = torch.empty(shape, dtype=x.dtype, device=x.device)
-        nws = query("dycon_conv_gemm_workspace", dt(x), mode, 0, B, D, H, W, Cin, N)
-        ws = _ws(nws, x)
-        rn = "conv_k3_tile" if (mode == CONV_K3 and Cin % 32 == 0 and Cin >= 64 and N % 128 == 0) else "conv_gemm_splitk"
-        taps = {CONV_K3: 27, CONV_K2S2: 8, CONV_1X1: 1}[mode]
-        with _Region(rn, (x.numel() + out.numel()) * _es(x) + taps * Cin * N * _es(x), 2 * (out.numel() // Cout) * taps * Cin * N):
-            call("dycon_conv_gemm_ex", _p(x), _p(wfrag), _p(bias), _p(out), dt(x), mode, 0, 0, B, D, H, W, Cin, N, Cout, _p(ws), nws, 1, _s())
-        return out, DeferredConv(ws, splits, bias)
     if out is None:
         assert not accumulate
         if scatter:
@@ -300,36 +308,22 @@ def conv_gemm(x, wfrag, bias, mode, N, Cout, scatter=False, out=None, accumulate
         else:
             shape = (B, D, H, W, N)
         out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    nws = query("dycon_conv_gemm_workspace", dt(x), mode, int(scatter), B, D, H, W, Cin, N)
+    nws = plan.workspace
     ws = _ws(nws, x) if nws else None
-    if PROFILER is None:      # hot path: no region bookkeeping (a step makes ~90 of these calls)
-        call("dycon_conv_gemm", _p(x), _p(wfrag), _p(bias), _p(out), dt(x), mode, int(scatter), int(accumulate),
-             B, D, H, W, Cin, N, Cout, _p(ws), nws, _s())
+    args = (_p(x), _p(wfrag), _p(bias), _p(out), dt(x), mode, int(scatter), int(accumulate), B, D, H, W, Cin, N, Cout, _p(ws), nws)
+    if PROFILER is None and not defer_finish:      # hot path: no region bookkeeping (a step makes ~90 of these calls)
+        call("dycon_conv_gemm", *args, _s())
         return out
-    taps = {CONV_K3: 27, CONV_K2S2: 8, CONV_1X1: 1}[mode]
     rows = out.numel() // Cout if not scatter else x.numel() // Cin
-    lds_path = mode == CONV_K3 and not scatter and conv_uses_lds(x, Cin, Cout)
-    if lds_path:      # the persistent kernels of the 16-channel level, or the generic LDS-halo kernel
-        rname = "conv_k3_p16" if (Cin, Cout) == (16, 16) else ("conv_k3_c1" if Cin == 1 else "conv_k3_lds")
-    elif (mode == CONV_K3 and not scatter and x.dtype == torch.bfloat16 and Cin == 128 and N % 128 == 0 and D * H * W < 13824
-          and not nws):
-        rname = "conv_k3_halo"      # the small levels' one-launch kernel (split-K ranges inside the workgroup: no workspace)
-    elif (mode == CONV_K3 and not scatter and x.dtype == torch.bfloat16 and Cin % 32 == 0 and Cin >= 64 and N % 128 == 0
-          and D * H * W < 13824):
-        rname = "conv_k3_tile"
-    else:
-        rname = "conv_gemm_splitk" if nws else "conv_gemm"
-    with _Region(rname, (x.numel() + out.numel() * (2 if accumulate else 1)) * _es(x) + taps * Cin * N * _es(x),
-                 2 * rows * taps * Cin * N):
-        call("dycon_conv_gemm", _p(x), _p(wfrag), _p(bias), _p(out), dt(x), mode, int(scatter), int(accumulate),
-             B, D, H, W, Cin, N, Cout, _p(ws), nws, _s())
-    return out
+    with _Region(plan.name, (x.numel() + out.numel() * (2 if accumulate else 1)) * _es(x) + _TAPS[mode] * Cin * N * _es(x),
+                 2 * rows * _TAPS[mode] * Cin * N):
+        call("dycon_conv_gemm_ex", *args, int(defer_finish), _s())
+    return (out, DeferredConv(ws, plan.splits, bias)) if defer_finish else out
 
 
 def conv_stats_chunks(x, Cin, Cout):
     """rows per sample of the statistics partials conv_gemm_stats writes for this k=3 shape (0: not served)"""
-    B, D, H, W, _ = x.shape
-    return query("dycon_conv_stats_chunks", dt(x), CONV_K3, B, D, H, W, Cin, Cout)
+    return conv_plan_for(x, CONV_K3, Cout, Cout).chunks
 
 
 def conv_gemm_stats(x, wfrag, bias, Cout, chunks):
@@ -337,8 +331,8 @@ def conv_gemm_stats(x, wfrag, bias, Cout, chunks):
     B, D, H, W, Cin = x.shape
     y = torch.empty((B, D, H, W, Cout), dtype=x.dtype, device=x.device)
     part = torch.empty(B * chunks * Cout * 2, dtype=torch.float32, device=x.device)
-    rname = "conv_k3_p16" if (Cin, Cout) == (16, 16) else ("conv_k3_c1" if Cin == 1 else "conv_k3_lds")
-    with _Region(rname, (x.numel() + y.numel()) * _es(x) + 27 * Cin * Cout * _es(x), 2 * (y.numel() // Cout) * 27 * Cin * Cout):
+    with _Region(conv_plan_for(x, CONV_K3, Cout, Cout).name, (x.numel() + y.numel()) * _es(x) + 27 * Cin * Cout * _es(x),
+                 2 * (y.numel() // Cout) * 27 * Cin * Cout):
         call("dycon_conv_gemm_stats", _p(x), _p(wfrag), _p(bias), _p(y), dt(x), B, D, H, W, Cin, Cout, _p(part), part.numel() * 4, _s())
     return y, part
 
@@ -349,7 +343,7 @@ def conv_direct(x, w_tcn, bias, mode, N, out_dtype, out=None, accumulate=False):
         assert not accumulate
         shape = (B, D // 2, H // 2, W // 2, N) if mode == CONV_K2S2 else (B, D, H, W, N)
         out = torch.empty(shape, dtype=out_dtype, device=x.device)
-    taps = {CONV_K3: 27, CONV_K2S2: 8, CONV_1X1: 1}[mode]
+    taps = _TAPS[mode]
     with _Region("conv_direct", x.numel() * _es(x) + out.numel() * _es(out), 2 * (out.numel() // N) * taps * Cin * N):
         call("dycon_conv_direct", _p(x), dt(x), _p(w_tcn), _p(bias), _p(out), dt(out), mode, int(accumulate),
              B, D, H, W, Cin, N, _s())
@@ -369,11 +363,9 @@ def conv_wgrad(x, gy, dw, mode, s_t, s_c, s_n, dbias=None, ws=None):
     Cout = gy.shape[-1]
     if ws is None:
         ws = _ws(query("dycon_conv_wgrad_workspace", mode, B, D, H, W, Cin, Cout), x)
-    taps = {CONV_K3: 27, CONV_K2S2: 8, CONV_1X1: 1}[mode]
-    k3bf = (x.dtype == torch.bfloat16 and gy.dtype == torch.bfloat16 and mode == CONV_K3 and (Cin % 16 == 0 or Cin == 1)
-            and (Cout in (16, 32) or Cout % 64 == 0))
-    with _Region("wgrad_k3_bf16" if k3bf else "conv_wgrad", x.numel() * _es(x) + gy.numel() * _es(gy) + taps * Cin * Cout * 4,
-                 2 * (gy.numel() // Cout) * taps * Cin * Cout):
+    taps = _TAPS[mode]
+    rname = "" if PROFILER is None else _lib.load().dycon_conv_wgrad_name(dt(x), dt(gy), mode, B, D, H, W, Cin, Cout).decode()
+    with _Region(rname, x.numel() * _es(x) + gy.numel() * _es(gy) + taps * Cin * Cout * 4, 2 * (gy.numel() // Cout) * taps * Cin * Cout):
         call("dycon_conv_wgrad", _p(x), dt(x), _p(gy), dt(gy), _p(dw), _p(dbias), mode, B, D, H, W, Cin, Cout, s_t, s_c, s_n,
              _p(ws), ws.numel() * 4, _s())
     return dw

@@ -78,14 +78,39 @@ int dycon_pack_tcn(const float* w, float* out, int T, int Cin, int N, int N0, lo
  * with wfrag packed as T=27, Cin=1 (K = 27 taps in one 32-wide k-step); Cin == 48 (U-Net
  * decoder) runs there with wfrag packed chunk-major: three T=27, Cin=16 packs of channels [0,16), [16,32),
  * [32,48) back to back.
- * workspace (optional, dycon_conv_gemm_workspace() bytes): enables split-K for the small spatial
- * levels (6^3, 12^3), whose few row blocks cannot fill 256 CUs: per-split fp32 slabs + ordered finish. */
+ * workspace (optional, `workspace` bytes of the plan below): enables split-K for the small spatial
+ * levels (6^3, 12^3), whose few row blocks cannot fill 256 CUs: per-split fp32 slabs + ordered finish.
+ *
+ * The plan.  Which kernel serves a shape, how many split-K slabs it leaves, the workspace it wants, whether it can take the
+ * statistics of its output and which weight packing it reads is decided in ONE place (csrc/conv.hip, conv_fwd_plan); the launch and
+ * every query below read that plan, and dycon_conv_gemm_plan hands it out (pure host code, no GPU needed):
+ *   family    DYCON_CONV_*: the kernel family (DYCON_CONV_NONE: a shape dycon_conv_gemm refuses)
+ *   splits    split-K slabs the caller sees (1: no workspace, no finish, defer_finish refused)
+ *   workspace bytes of those slabs (0 when splits == 1)
+ *   chunks    rows per sample of the statistics partials dycon_conv_gemm_stats writes (0: family cannot, or accumulate set)
+ *   weights   DYCON_CONV_W_FRAG: one dycon_pack_bfrag pack; DYCON_CONV_W_CHUNK16: the chunk-major Cin == 48 packing above
+ * dycon_conv_kernel_name gives the family's kernel name without the _kernel suffix; dycon_conv_region_name the name of one call
+ * for a profile (the same, except conv_gemm_splitk for DYCON_CONV_GEMM with splits > 1: kernel + finish).  The three older queries
+ * return one field each, and answer for a refused shape as they always have (the generic kernel's split plan). */
+enum {
+    DYCON_CONV_NONE = 0, DYCON_CONV_C1, DYCON_CONV_P16, DYCON_CONV_P32, DYCON_CONV_LDS, DYCON_CONV_HALO, DYCON_CONV_TILE,
+    DYCON_CONV_GEMM
+};
+enum { DYCON_CONV_W_FRAG = 0, DYCON_CONV_W_CHUNK16 = 1 };
+typedef struct {
+    int family, splits, chunks, weights;
+    size_t workspace;
+} dycon_conv_plan_t;
+int dycon_conv_gemm_plan(int dtype, int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin, int N,
+                         int Cout, dycon_conv_plan_t* plan);
+const char* dycon_conv_kernel_name(int family);
+const char* dycon_conv_region_name(const dycon_conv_plan_t* plan);
 size_t dycon_conv_gemm_workspace(int dtype, int mode, int scatter, int B, int Di, int Hi, int Wi,
                                  int Cin, int N);
 int dycon_conv_gemm(const void* x, const void* wfrag, const float* bias, void* y, int dtype,
                     int mode, int scatter, int accumulate, int B, int Di, int Hi, int Wi, int Cin,
                     int N, int Cout, float* workspace, size_t ws_bytes, dycon_stream_t stream);
-/* dycon_conv_gemm with defer_finish: on a split-K shape (dycon_conv_gemm_splits() > 1, workspace given, no accumulation) the
+/* dycon_conv_gemm with defer_finish: on a split-K shape (plan splits > 1, workspace given, no accumulation; DYCON_ERR_INVALID otherwise) the
  * partial slabs stay in `workspace` ([split][row][N] fp32) and no finish is launched; the convolution is completed by
  * dycon_norm_fwd_slab, which fuses bias + ordered slab sum + rounding with the GroupNorm / InstanceNorm that follows
  * (VNet.py:16-23 at the 12^3 / 6^3 levels): one launch less on the step's critical chain, bit-identical results. */
@@ -106,6 +131,8 @@ int dycon_conv_direct(const void* x, int x_dtype, const float* w_tcn, const floa
  * pass over gy on the bf16 k=3 path).  Two-stage, deterministic: per-split partials in
  * `workspace`, then an ordered reduce. */
 size_t dycon_conv_wgrad_workspace(int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout);
+/* the kernel dycon_conv_wgrad runs for these dtypes and this shape, named without the _kernel suffix (pure host code) */
+const char* dycon_conv_wgrad_name(int x_dtype, int g_dtype, int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout);
 int dycon_conv_wgrad(const void* x, int x_dtype, const void* gy, int g_dtype, float* dw, float* dbias,
                      int mode, int B, int Di, int Hi, int Wi, int Cin, int Cout, long long s_t,
                      long long s_c, long long s_n, float* workspace, size_t ws_bytes,

@@ -116,3 +116,19 @@ def test_step_has_no_outside_switches():
     bools = {f.name for f in dataclasses.fields(TrainConfig) if isinstance(f.default, bool)}
     assert bools == {"poly_lr", "strict_nan_check", "global_batch_losses", "overlap_teacher", "overlap_wgrad", "overlap_features",
                      "use_aspp", "ddp_force", "replay"}, bools
+
+
+def test_conv_dispatch_is_decided_in_one_place():
+    """The forward convolution's kernel choice lives in conv_fwd_plan (csrc/conv.hip) alone: the 24^3 threshold is one named constant
+    there and appears in no Python file of the package, the statistics buffer is an argument and not thread-local state, and ops no
+    longer restates the LDS-halo predicate."""
+    from dycon_paper_replication_amd import ops
+    pkg = os.path.join(ROOT, "dycon_paper_replication_amd")
+    hits = []
+    for d, _, files in os.walk(pkg):
+        hits += [os.path.join(d, f) for f in files if f.endswith(".py") and "13824" in open(os.path.join(d, f)).read()]
+    assert not hits, hits
+    conv = open(os.path.join(pkg, "csrc", "conv.hip")).read()
+    assert conv.count("13824") == 1
+    assert "thread_local" not in conv
+    assert not hasattr(ops, "conv_uses_lds")

@@ -43,7 +43,7 @@ for S, C in ((96, 16), (48, 32), (24, 64), (12, 128), (6, 256)):
     both(f"norm_bwd GN {C}ch @{S}^3", lambda: ops.norm_bwd(x, False, gy, stats, B, V, C, 16, gamma, beta, True, dg, db), 5 * nb)
     w = torch.randn(C, C, 3, 3, 3, device=dev) * 0.02
     b = torch.zeros(C, device=dev)
-    if ops.conv_uses_lds(x, C, C) or C >= 64:
+    if ops.conv_plan_for(x, CONV_K3, C, C).name.startswith("conv_k3") or C >= 64:
         wf = ops.pack_bfrag(w, torch.bfloat16, 27, C, C, C, 1, 27, 0, C * 27)
         both(f"conv k3 {C}->{C} @{S}^3", lambda: ops.conv_gemm(x, wf, b, CONV_K3, C, C), 2 * nb, 2 * B * V * 27 * C * C)
     gw, gb = torch.empty_like(w), torch.empty_like(b)
