@@ -51,6 +51,10 @@ SIGNATURES = {
     "dycon_norm_head_fwd": (I, [P, I, I, L, I, P, P, P, I, P, P, P, P, P]),
     "dycon_norm_head_bwd": (I, [P, P, P, I, I, L, I, P, P, P, I, P, P, P, P, P, Z, P]),
     "dycon_norm_head_dparams": (I, [P, I, L, P, P, P]),
+    "dycon_norm_headc_workspace": (Z, [I, L, I]),
+    "dycon_norm_headc_fwd": (I, [P, I, I, L, I, I, P, P, P, I, P, P, P, P, P]),
+    "dycon_norm_headc_bwd": (I, [P, P, P, I, I, L, I, I, P, P, P, I, P, P, P, P, P, Z, P]),
+    "dycon_norm_headc_dparams": (I, [P, I, L, I, P, P, P]),
     "dycon_conv_stats_chunks": (I, [I, I, I, I, I, I, I, I]),
     "dycon_conv_gemm_stats": (I, [P, P, P, P, I, I, I, I, I, I, I, P, Z, P]),
     "dycon_norm_fwd_parts": (I, [P, P, I, I, L, I, I, F, P, P, P, I, P, P, P, P, F, P, I, P]),
@@ -101,6 +105,8 @@ SIGNATURES = {
     "dycon_kl_rows_bwd": (I, [P, L, P, L, L, L, L, I, P, P, L, P]),
     "dycon_focal_fwd": (I, [P, P, I, L, I, L, F, P, I, P, P, P]),
     "dycon_focal_bwd": (I, [P, P, I, L, I, L, F, P, I, P, P, P]),
+    "dycon_uncl_fwd": (I, [P, P, L, I, L, F, P, P, P]),
+    "dycon_uncl_bwd": (I, [P, P, L, I, L, F, P, P, P]),
     "dycon_l2norm_fwd": (I, [P, P, P, I, L, I, F, P]),
     "dycon_l2norm_bwd": (I, [P, P, P, P, I, L, I, F, P]),
     "dycon_mask_pool": (I, [P, I, P, I, I, I, I, I, I, I, P]),
@@ -121,6 +127,7 @@ SIGNATURES = {
     "dycon_sgd_ema": (I, [P, P, P, P, L, L, P, F, F, F, F, F, F, P, P]),
     "dycon_nonfinite_flag": (I, [P, P, P]),
     "dycon_sw_accumulate": (I, [P, I, I, I, I, P, P, P, I, I, I, P]),
+    "dycon_sw_accumulate_c": (I, [P, I, I, I, I, I, P, P, P, I, I, I, P]),
     "dycon_sw_finalize": (I, [P, P, L, F, P, P, P]),
     "dycon_binary_overlap": (I, [P, P, I, L, P, P]),
     "dycon_batch_overlap": (I, [P, P, I, I, L, P, P]),

@@ -60,6 +60,15 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float f) {
     return *reinterpret_cast<unsigned short*>(&h);
 }
 
+// c + a * b of the unfused class heads' 16 <-> K products (csrc/conv.hip head_1x1_*).  K = 2 keeps the plain expression of the DyCON
+// step's kernels (the fused 2-class head of csrc/norm.hip is written the same way and the compiler contracts both alike: pinned by
+// tests/test_ops_gpu.py); every other K is an explicit fused multiply-add, as in the class-count head kernels of csrc/norm.hip,
+// so the fused and the unfused kernels round alike whatever surrounds the expression.
+template <int K> __device__ __forceinline__ float head_madd(float a, float b, float c) {
+    if constexpr (K == 2) return c + a * b;
+    else return fmaf(a, b, c);
+}
+
 // 16-byte vector of T: 4 floats or 8 bf16
 template <typename T> struct Vec16;
 template <> struct Vec16<float> {

@@ -2607,8 +2607,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(const TX* __rest
     part[(long long)blockIdx.x * L + j] = acc;
 }
 
-// 1x1 weight gradient for the 2-class heads (Cin = 16, Cout = 2): every thread keeps all CIN*COUT partial
-// products in registers over a strided voxel stream (one 32-B + one 8-B load per voxel), block-reduces them
+// 1x1 weight gradient for the class heads (Cin = 16, Cout = 1..8 classes): every thread keeps all CIN*COUT partial
+// products in registers over a strided voxel stream (one 32-B load + one row of logit gradients per voxel), block-reduces them
 // through LDS and writes one partial row.  Pure HBM stream.
 template <typename TX, typename TG, int CIN, int COUT>
 __global__ __launch_bounds__(256) void wgrad_1x1_skinny_kernel(const TX* __restrict__ X, const TG* __restrict__ GY,
@@ -2644,7 +2644,7 @@ __global__ __launch_bounds__(256) void wgrad_1x1_skinny_kernel(const TX* __restr
         part[(long long)blockIdx.x * CIN * COUT + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// y[m, 0..COUT) = bias + sum_c x[m, c] * W[c][.]   (Cin = 16 -> 2 logits: one 32-B load per voxel)
+// y[m, 0..COUT) = bias + sum_c x[m, c] * W[c][.]   (Cin = 16 -> 1..8 logits: one 32-B load per voxel)
 template <typename TI, int CIN, int COUT>
 __global__ __launch_bounds__(256) void head_1x1_fwd_kernel(const TI* __restrict__ X, const float* __restrict__ W,
                                                            const float* __restrict__ bias, float* __restrict__ Y, long long M) {
@@ -2663,14 +2663,14 @@ __global__ __launch_bounds__(256) void head_1x1_fwd_kernel(const TI* __restrict_
 #pragma unroll
             for (int e = 0; e < VN; ++e)
 #pragma unroll
-                for (int k = 0; k < COUT; ++k) o[k] += v.get(e) * w[(c0 + e) * COUT + k];
+                for (int k = 0; k < COUT; ++k) o[k] = head_madd<COUT>(v.get(e), w[(c0 + e) * COUT + k], o[k]);
         }
 #pragma unroll
         for (int k = 0; k < COUT; ++k) Y[m * COUT + k] = o[k];
     }
 }
 
-// gx[m, 0..COUT) = sum_k g[m, k] * W[k][.]   (2 logit gradients -> 16 channels, 16-B stores)
+// gx[m, 0..COUT) = sum_k g[m, k] * W[k][.]   (1..8 logit gradients -> 16 channels, 16-B stores)
 template <typename TO, int CIN, int COUT>
 __global__ __launch_bounds__(256) void head_1x1_bwd_kernel(const float* __restrict__ G, const float* __restrict__ W,
                                                            TO* __restrict__ Y, long long M, int accumulate) {
@@ -2690,7 +2690,7 @@ __global__ __launch_bounds__(256) void head_1x1_bwd_kernel(const float* __restri
             for (int e = 0; e < VN; ++e) {
                 float v = accumulate ? o.get(e) : 0.f;
 #pragma unroll
-                for (int k = 0; k < CIN; ++k) v += g[k] * w[k * COUT + c0 + e];
+                for (int k = 0; k < CIN; ++k) v = head_madd<CIN>(g[k], w[k * COUT + c0 + e], v);
                 o.set(e, v);
             }
             st16(Y + m * COUT + c0, o);
@@ -3192,19 +3192,29 @@ extern "C" int dycon_conv_direct(const void* x, int x_dtype, const float* w_tcn,
     DYCON_REQUIRE(x && w_tcn && y, "conv_direct: null pointer");
     DYCON_REQUIRE(B > 0 && Di > 0 && Hi > 0 && Wi > 0 && Cin > 0 && N > 0, "conv_direct: bad shape");
     DYCON_REQUIRE(mode >= 0 && mode <= 2, "conv_direct: bad mode %d", mode);
-    if (mode == DYCON_CONV_1X1) {   // the 2-class heads: vectorised streaming kernels
+    if (mode == DYCON_CONV_1X1) {   // the class heads (1..8 logits): vectorised streaming kernels
         const long long M = (long long)B * Di * Hi * Wi;
         long long blocks = (M + 255) / 256;
         if (blocks > 4096) blocks = 4096;
-        if (Cin == 16 && N == 2 && y_dtype == DYCON_F32 && !accumulate) {
-            if (x_dtype == DYCON_F32) head_1x1_fwd_kernel<float, 16, 2><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, bias, (float*)y, M);
-            else head_1x1_fwd_kernel<bf16, 16, 2><<<(int)blocks, 256, 0, stream>>>((const bf16*)x, w_tcn, bias, (float*)y, M);
+        if (Cin == 16 && N >= 1 && N <= 8 && y_dtype == DYCON_F32 && !accumulate) {
+#define DYCON_HF(K)                                                                                                                    \
+    case K:                                                                                                                            \
+        if (x_dtype == DYCON_F32) head_1x1_fwd_kernel<float, 16, K><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, bias, (float*)y, M); \
+        else head_1x1_fwd_kernel<bf16, 16, K><<<(int)blocks, 256, 0, stream>>>((const bf16*)x, w_tcn, bias, (float*)y, M);             \
+        break
+            switch (N) { DYCON_HF(1); DYCON_HF(2); DYCON_HF(3); DYCON_HF(4); DYCON_HF(5); DYCON_HF(6); DYCON_HF(7); DYCON_HF(8); }
+#undef DYCON_HF
             DYCON_LAUNCH_CHECK();
             return DYCON_OK;
         }
-        if (Cin == 2 && N == 16 && x_dtype == DYCON_F32 && !bias) {
-            if (y_dtype == DYCON_F32) head_1x1_bwd_kernel<float, 2, 16><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, (float*)y, M, accumulate);
-            else head_1x1_bwd_kernel<bf16, 2, 16><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, (bf16*)y, M, accumulate);
+        if (Cin >= 1 && Cin <= 8 && N == 16 && x_dtype == DYCON_F32 && !bias) {
+#define DYCON_HB(K)                                                                                                                    \
+    case K:                                                                                                                            \
+        if (y_dtype == DYCON_F32) head_1x1_bwd_kernel<float, K, 16><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, (float*)y, M, accumulate); \
+        else head_1x1_bwd_kernel<bf16, K, 16><<<(int)blocks, 256, 0, stream>>>((const float*)x, w_tcn, (bf16*)y, M, accumulate);       \
+        break
+            switch (Cin) { DYCON_HB(1); DYCON_HB(2); DYCON_HB(3); DYCON_HB(4); DYCON_HB(5); DYCON_HB(6); DYCON_HB(7); DYCON_HB(8); }
+#undef DYCON_HB
             DYCON_LAUNCH_CHECK();
             return DYCON_OK;
         }
@@ -3326,7 +3336,7 @@ static WgradPlan wgrad_plan(int x_dtype, int g_dtype, int mode, int B, int Di, i
             p.family = WG_1X1;
         }
         if (p.family <= WG_1X1) p.rows = p.family == WG_C1 ? wgrad_c1_wgs(B, Di, Hi, Wi) : p.k.splits;
-    } else if (mode == DYCON_CONV_1X1 && Cin == 16 && Cout == 2 && g_dtype == DYCON_F32) {     // the 2-class head: at most 1024 rows
+    } else if (mode == DYCON_CONV_1X1 && Cin == 16 && Cout >= 1 && Cout <= 8 && g_dtype == DYCON_F32) {     // the C-class heads (C in 1..8): at most 1024 rows
         p.family = WG_SKINNY;
         if (p.rows > 1024) p.rows = 1024;
     }
@@ -3455,8 +3465,13 @@ extern "C" int dycon_conv_wgrad(const void* x, int x_dtype, const void* gy, int 
 #undef DYCON_W11
         break;
     case WG_SKINNY:
-        if (x_dtype == DYCON_F32) wgrad_1x1_skinny_kernel<float, float, 16, 2><<<p.rows, 256, 0, stream>>>((const float*)x, (const float*)gy, workspace, M);
-        else wgrad_1x1_skinny_kernel<bf16, float, 16, 2><<<p.rows, 256, 0, stream>>>(xp, (const float*)gy, workspace, M);
+#define DYCON_WSK(CO)                                                                                                                  \
+    case CO:                                                                                                                           \
+        if (x_dtype == DYCON_F32) wgrad_1x1_skinny_kernel<float, float, 16, CO><<<p.rows, 256, 0, stream>>>((const float*)x, (const float*)gy, workspace, M); \
+        else wgrad_1x1_skinny_kernel<bf16, float, 16, CO><<<p.rows, 256, 0, stream>>>(xp, (const float*)gy, workspace, M);             \
+        break
+        switch (Cout) { DYCON_WSK(1); DYCON_WSK(2); DYCON_WSK(3); DYCON_WSK(4); DYCON_WSK(5); DYCON_WSK(6); DYCON_WSK(7); DYCON_WSK(8); }
+#undef DYCON_WSK
         break;
     default:
         if (x_dtype == DYCON_F32 && g_dtype == DYCON_F32) launch_wgrad<float, float>(x, gy, workspace, mode, p, B, Di, Hi, Wi, Cin, Cout, stream);

@@ -881,17 +881,55 @@ extern "C" int dycon_norm_bwd_ex(const void* src, int from_y, const void* gy, vo
 // Arithmetic per voxel is that of norm_apply_kernel / head_1x1_fwd_kernel / head_1x1_bwd_kernel, including the rounding of y and
 // gy to the storage type: the logits are the unfused path's bit for bit, gz to fp32 round-off; dW / db differ in summation order.
 // ------------------------------------------------------------------------------------------------
-constexpr int HC = 16, HK = 2;                      // channels in, logits out
-constexpr int HPART = HK * HC + HK;                 // per-chunk head partials: dW[k][c], db[k]
+// Two sets of kernels.  The class-count kernels (norm_apply_headc_kernel & co., dycon_norm_headc_*) are templates over the class
+// count HK (1..8, the reference's class_num): a row of logits / logit gradients is HK fp32 values; for HK = 1 a thread keeps the
+// head's weights in registers, for wider heads HK x 16 weights next to sc / sh / dr would not fit, so they are read from LDS (same
+// address in all lanes of the forward: a broadcast).  VGPR counts per instantiation: DESIGN.md section 7.  The 2-class kernels of
+// the DyCON step (norm_apply_head_kernel & co., dycon_norm_head_*, further down) are the kernels the step has always launched,
+// kept as they were; the class-count entry points hand classes = 2 to them, so HK = 2 is never instantiated.
+constexpr int HC = 16;                              // channels in
+constexpr int HK_MAX = 8;                           // most logits out
+constexpr int hpart_len(int hk) { return hk * HC + hk; }   // per-chunk head partials: dW[k][c], db[k]
 
 template <typename T> __device__ __forceinline__ float round_to(float v) { T t; stf(&t, v); return ldf(&t); }
 
-template <typename T>
-__global__ __launch_bounds__(256) void norm_apply_head_kernel(const T* __restrict__ X, long long V, int G,
-                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, int relu,
-                                                              const float* __restrict__ chan_scale, const float* __restrict__ W,
-                                                              const float* __restrict__ hb, float* __restrict__ L) {
+// one row of HK fp32 values: the widest aligned access the row length allows (16 bytes for 4 and 8, 8 for 6, else 4)
+template <int HK> __device__ __forceinline__ void ld_row(const float* __restrict__ p, float (&r)[HK]) {
+    if constexpr (HK % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < HK; k += 4) {
+            const float4 t = *reinterpret_cast<const float4*>(p + k);
+            r[k] = t.x; r[k + 1] = t.y; r[k + 2] = t.z; r[k + 3] = t.w;
+        }
+    } else if constexpr (HK % 2 == 0) {
+#pragma unroll
+        for (int k = 0; k < HK; k += 2) {
+            const float2 t = *reinterpret_cast<const float2*>(p + k);
+            r[k] = t.x; r[k + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < HK; ++k) r[k] = p[k];
+    }
+}
+template <int HK> __device__ __forceinline__ void st_row(float* __restrict__ p, const float (&r)[HK]) {
+    if constexpr (HK % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < HK; k += 4) *reinterpret_cast<float4*>(p + k) = make_float4(r[k], r[k + 1], r[k + 2], r[k + 3]);
+    } else if constexpr (HK % 2 == 0) {
+#pragma unroll
+        for (int k = 0; k < HK; k += 2) *reinterpret_cast<float2*>(p + k) = make_float2(r[k], r[k + 1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < HK; ++k) p[k] = r[k];
+    }
+}
+
+template <typename T, int HK>
+__device__ __forceinline__ void norm_apply_head_body(const T* __restrict__ X, long long V, int G, const float* __restrict__ stats,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta, int relu,
+                                                     const float* __restrict__ chan_scale, const float* __restrict__ W,
+                                                     const float* __restrict__ hb, float* __restrict__ L) {
     constexpr int VN = Vec16<T>::N;
     __shared__ float ss[3 * HC + HK * HC + HK];
     const int n = blockIdx.y, cpg = HC / G;
@@ -906,10 +944,360 @@ __global__ __launch_bounds__(256) void norm_apply_head_kernel(const T* __restric
     if (threadIdx.x < HK * HC) ss[3 * HC + threadIdx.x] = W[threadIdx.x];
     if (threadIdx.x < HK) ss[3 * HC + HK * HC + threadIdx.x] = hb ? hb[threadIdx.x] : 0.f;
     __syncthreads();
+    constexpr bool WREG = HK == 1;                   // weights in registers
+    float sc[HC], sh[HC], dr[HC], wr[WREG ? HK * HC : 1], hbias[HK];
+#pragma unroll
+    for (int c = 0; c < HC; ++c) { sc[c] = ss[c]; sh[c] = ss[HC + c]; dr[c] = ss[2 * HC + c]; }
+    if constexpr (WREG) {
+#pragma unroll
+        for (int j = 0; j < HK * HC; ++j) wr[j] = ss[3 * HC + j];
+    }
+#pragma unroll
+    for (int k = 0; k < HK; ++k) hbias[k] = ss[3 * HC + HK * HC + k];
+    const float* wl = ss + 3 * HC;
+    const T* xp = X + (long long)n * V * HC;
+    float* lp = L + (long long)n * V * HK;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+        float o[HK];
+#pragma unroll
+        for (int k = 0; k < HK; ++k) o[k] = hbias[k];
+#pragma unroll
+        for (int c0 = 0; c0 < HC; c0 += VN) {
+            const Vec16<T> x = ld16(xp + v * HC + c0);
+#pragma unroll
+            for (int k = 0; k < VN; ++k) {
+                const int c = c0 + k;
+                float y = x.get(k) * sc[c] + sh[c];
+                if (relu) y = y < 0.f ? 0.f : y;
+                y = round_to<T>(y * dr[c]);          // what norm_apply_kernel would have stored
+#pragma unroll
+                for (int kk = 0; kk < HK; ++kk) o[kk] = fmaf(y, WREG ? wr[WREG ? kk * HC + c : 0] : wl[kk * HC + c], o[kk]);
+            }
+        }
+        st_row<HK>(lp + v * HK, o);
+    }
+}
+template <typename T, int HK>
+__global__ __launch_bounds__(256) void norm_apply_headc_kernel(const T* __restrict__ X, long long V, int G,
+                                                               const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                               const float* __restrict__ beta, int relu,
+                                                               const float* __restrict__ chan_scale, const float* __restrict__ W,
+                                                               const float* __restrict__ hb, float* __restrict__ L) {
+    norm_apply_head_body<T, HK>(X, V, G, stats, gamma, beta, relu, chan_scale, W, hb, L);
+}
+
+// statistics pass of the backward: thread mapping, row order and summation order of norm_partial_kernel<T, 1>, with gy formed on the fly;
+// additionally the head's weight / bias gradient partials of the chunk (hpart[(n, chunk)][hpart_len(HK)]).
+// A thread carries 2 + HK sums per channel; they go through LDS four at a time.
+template <typename T, int HK>
+__device__ __forceinline__ void norm_head_partial_body(const T* __restrict__ S, const float* __restrict__ GL, float* __restrict__ part,
+                                                       float* __restrict__ hpart, long long V, int G, long long rows_per_chunk,
+                                                       const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, int relu, const float* __restrict__ chan_scale,
+                                                       const float* __restrict__ W) {
+    constexpr int VN = Vec16<T>::N;
+    constexpr int NGRP = HC / VN, RPI = 256 / NGRP;
+    constexpr int NQ = 2 + HK;                       // sums per channel: g, g * xhat, gl_k * y
+    constexpr int NR = NQ < 4 ? NQ : 4;              // of which NR go through LDS per round
+    constexpr int HPART = hpart_len(HK);
+    constexpr bool WREG = HK == 1;
+    __shared__ float sm[NR][256][VN + 1];
+    __shared__ float sb[256][HK];
+    __shared__ float sw[WREG ? 1 : HK * HC];
+    const int n = blockIdx.y, chunk = blockIdx.x;
+    const int cg = threadIdx.x % NGRP, rr = threadIdx.x / NGRP;
+    const long long v0 = chunk * rows_per_chunk, v1 = min(V, v0 + rows_per_chunk);
+    const int cpg = HC / G;
+    if constexpr (!WREG) {
+        if (threadIdx.x < HK * HC) sw[threadIdx.x] = W[threadIdx.x];
+        __syncthreads();
+    }
+    float acc[NQ][VN], e[HK];
+    float mean[VN], rstd[VN], gm[VN], bt[VN], cs[VN], sc[VN], sh[VN], wr[WREG ? HK : 1][VN];
+#pragma unroll
+    for (int kk = 0; kk < HK; ++kk) e[kk] = 0.f;
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        const int c = cg * VN + k, g = c / cpg;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) acc[q][k] = 0.f;
+        cs[k] = chan_scale ? chan_scale[(long long)n * HC + c] : 1.f;
+        mean[k] = stats[((long long)n * G + g) * 2];
+        rstd[k] = stats[((long long)n * G + g) * 2 + 1];
+        gm[k] = gamma ? gamma[c] : 1.f;
+        bt[k] = beta ? beta[c] : 0.f;
+        sc[k] = rstd[k] * gm[k];
+        sh[k] = bt[k] - mean[k] * rstd[k] * gm[k];
+        if constexpr (WREG) {
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) wr[kk][k] = W[kk * HC + c];
+        }
+    }
+    const float* wl = sw + cg * VN;
+    const T* sp = S + ((long long)n * V) * HC + cg * VN;
+    const float* gp = GL + (long long)n * V * HK;
+    for (long long v = v0 + rr; v < v1; v += RPI) {
+        const Vec16<T> s = ld16(sp + v * HC);
+        float gl[HK];
+        ld_row<HK>(gp + v * HK, gl);
+#pragma unroll
+        for (int k = 0; k < VN; ++k) {
+            float gyv = 0.f;                         // head_1x1_bwd_kernel's order and rounding
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) gyv = fmaf(gl[kk], WREG ? wr[WREG ? kk : 0][k] : wl[kk * HC + k], gyv);
+            float g = round_to<T>(gyv) * cs[k];
+            const float x = s.get(k);
+            const float xh = (x - mean[k]) * rstd[k];
+            if (relu && !(gm[k] * xh + bt[k] > 0.f)) g = 0.f;
+            acc[0][k] += g;
+            acc[1][k] += g * xh;
+            float y = x * sc[k] + sh[k];             // the forward's y (norm_apply_head_kernel)
+            if (relu) y = y < 0.f ? 0.f : y;
+            y = round_to<T>(y * cs[k]);
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) acc[2 + kk][k] += gl[kk] * y;
+        }
+        if (cg == 0) {
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) e[kk] += gl[kk];
+        }
+    }
+#pragma unroll
+    for (int kk = 0; kk < HK; ++kk) sb[threadIdx.x][kk] = e[kk];
+    const long long item = (long long)n * gridDim.x + chunk;
+#pragma unroll
+    for (int r0 = 0; r0 < NQ; r0 += NR) {
+        if (r0) __syncthreads();                     // the previous round has been read
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            if (r0 + j < NQ) {
+#pragma unroll
+                for (int k = 0; k < VN; ++k) sm[j][threadIdx.x][k] = acc[r0 + j < NQ ? r0 + j : 0][k];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < NR * HC) {
+            const int j = threadIdx.x / HC, o = threadIdx.x % HC, og = o / VN, ok = o % VN, q = r0 + j;
+            if (q < NQ) {
+                float s0 = 0.f;
+                for (int i = 0; i < RPI; ++i) s0 += sm[j][i * NGRP + og][ok];
+                if (q < 2) part[((item * HC) + o) * 2 + q] = s0;     // {sum g, sum g*xhat} per channel, as norm_partial_kernel stores them
+                else hpart[item * HPART + (q - 2) * HC + o] = s0;
+            }
+        } else if (r0 == 0 && threadIdx.x >= 128 && threadIdx.x < 128 + HK) {
+            const int kk = threadIdx.x - 128;
+            float s0 = 0.f;
+            for (int i = 0; i < 256; ++i) s0 += sb[i][kk];
+            hpart[item * HPART + HK * HC + kk] = s0;
+        }
+    }
+}
+template <typename T, int HK>
+__global__ __launch_bounds__(256) void norm_head_partialc_kernel(const T* __restrict__ S, const float* __restrict__ GL,
+                                                                 float* __restrict__ part, float* __restrict__ hpart, long long V,
+                                                                 int G, long long rows_per_chunk, const float* __restrict__ stats,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 int relu, const float* __restrict__ chan_scale,
+                                                                 const float* __restrict__ W) {
+    norm_head_partial_body<T, HK>(S, GL, part, hpart, V, G, rows_per_chunk, stats, gamma, beta, relu, chan_scale, W);
+}
+
+// sums of the head partials over all (n, chunk): one workgroup per output (hpart_len of them)
+__global__ __launch_bounds__(256) void norm_headc_finalize_kernel(const float* __restrict__ hpart, int items, int hk,
+                                                                 float* __restrict__ dW, float* __restrict__ db) {
+    const int j = blockIdx.x, hpart_n = hpart_len(hk);
+    double s0 = 0.0, s1 = 0.0;
+    for (int e = threadIdx.x; e < items; e += 256) s0 += hpart[(long long)e * hpart_n + j];
+    block_sum2_double(s0, s1);
+    if (threadIdx.x == 0) {
+        if (j < hk * HC) { if (dW) dW[j] = (float)s0; }
+        else if (db) db[j - hk * HC] = (float)s0;
+    }
+}
+
+template <typename T, int HK>
+__device__ __forceinline__ void norm_head_bwd_apply_body(const T* __restrict__ S, const float* __restrict__ GL, T* __restrict__ GX,
+                                                         long long V, int G, const float* __restrict__ stats,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                         const float* __restrict__ ab, int relu, const float* __restrict__ chan_scale,
+                                                         const float* __restrict__ W) {
+    constexpr int VN = Vec16<T>::N;
+    constexpr int NGRP = HC / VN;
+    constexpr bool WREG = HK == 1;
+    __shared__ float sw[WREG ? 1 : HK * HC];
+    if constexpr (!WREG) {
+        if (threadIdx.x < HK * HC) sw[threadIdx.x] = W[threadIdx.x];
+        __syncthreads();
+    }
+    const int n = blockIdx.y, cpg = HC / G;
+    const float inv_cnt = 1.f / ((float)V * (float)cpg);
+    const long long total = V * NGRP;
+    // 256 * VN is a multiple of 16: a thread's channels never change
+    const int cg = threadIdx.x % NGRP;
+    float mu[VN], rs[VN], gmv[VN], btv[VN], pa[VN], pb[VN], dr[VN], wr[WREG ? HK : 1][VN];
+#pragma unroll
+    for (int k = 0; k < VN; ++k) {
+        const int c = cg * VN + k, g = c / cpg;
+        mu[k] = stats[((long long)n * G + g) * 2];
+        rs[k] = stats[((long long)n * G + g) * 2 + 1];
+        gmv[k] = gamma ? gamma[c] : 1.f;
+        btv[k] = beta ? beta[c] : 0.f;
+        pa[k] = ab[((long long)n * G + g) * 2] * inv_cnt;
+        pb[k] = ab[((long long)n * G + g) * 2 + 1] * inv_cnt;
+        dr[k] = chan_scale ? chan_scale[(long long)n * HC + c] : 1.f;
+        if constexpr (WREG) {
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) wr[kk][k] = W[kk * HC + c];
+        }
+    }
+    const float* wl = sw + cg * VN;
+    const long long base = (long long)n * V * HC;
+    const float* gp = GL + (long long)n * V * HK;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const Vec16<T> s = ld16(S + base + i * VN);
+        float gl[HK];
+        ld_row<HK>(gp + (i / NGRP) * HK, gl);
+        Vec16<T> o;
+#pragma unroll
+        for (int k = 0; k < VN; ++k) {
+            float gyv = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < HK; ++kk) gyv = fmaf(gl[kk], WREG ? wr[WREG ? kk : 0][k] : wl[kk * HC + k], gyv);
+            float g = round_to<T>(gyv) * dr[k];
+            const float xh = (s.get(k) - mu[k]) * rs[k];
+            if (relu && !(gmv[k] * xh + btv[k] > 0.f)) g = 0.f;
+            o.set(k, rs[k] * (gmv[k] * g - (pa[k] + xh * pb[k])));
+        }
+        st16(GX + base + i * VN, o);
+    }
+}
+template <typename T, int HK>
+__global__ __launch_bounds__(256) void norm_head_bwd_applyc_kernel(const T* __restrict__ S, const float* __restrict__ GL,
+                                                                   T* __restrict__ GX, long long V, int G,
+                                                                   const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                                   const float* __restrict__ beta, const float* __restrict__ ab,
+                                                                   int relu, const float* __restrict__ chan_scale,
+                                                                   const float* __restrict__ W) {
+    norm_head_bwd_apply_body<T, HK>(S, GL, GX, V, G, stats, gamma, beta, ab, relu, chan_scale, W);
+}
+
+// the class count of a launch picks the instantiation
+#define DYCON_HEAD_K(HKV, ...)                                                       \
+    switch (HKV) {                                                                   \
+    case 1: { constexpr int HK = 1; __VA_ARGS__; } break;                            \
+    case 3: { constexpr int HK = 3; __VA_ARGS__; } break;                            \
+    case 4: { constexpr int HK = 4; __VA_ARGS__; } break;                            \
+    case 5: { constexpr int HK = 5; __VA_ARGS__; } break;                            \
+    case 6: { constexpr int HK = 6; __VA_ARGS__; } break;                            \
+    case 7: { constexpr int HK = 7; __VA_ARGS__; } break;                            \
+    default: { constexpr int HK = 8; __VA_ARGS__; } break;                           \
+    }
+
+static int head_check(const char* who, int classes) {
+    DYCON_REQUIRE(classes >= 1 && classes <= HK_MAX, "%s: classes = %d (1..%d)", who, classes, HK_MAX);
+    return DYCON_OK;
+}
+
+// classes = 2 is the DyCON step's head: its own kernels (further down), so the two sets of entry points give the same bits
+extern "C" size_t dycon_norm_headc_workspace(int Nb, long long V, int classes) {
+    if (classes < 1 || classes > HK_MAX) return 0;
+    const NormPlan p = norm_plan(V);
+    return dycon_norm_workspace(Nb, V, HC) + (size_t)Nb * p.chunks * hpart_len(classes) * sizeof(float);
+}
+
+extern "C" int dycon_norm_headc_fwd(const void* x, int dtype, int Nb, long long V, int G, int classes, const float* stats,
+                                    const float* gamma, const float* beta, int relu, const float* chan_scale, const float* head_w,
+                                    const float* head_b, float* logits, dycon_stream_t stream) {
+    DYCON_REQUIRE(x && stats && head_w && logits, "norm_head_fwd: null pointer");
+    if (int e = head_check("norm_head_fwd", classes)) return e;
+    if (classes == 2) return dycon_norm_head_fwd(x, dtype, Nb, V, G, stats, gamma, beta, relu, chan_scale, head_w, head_b, logits, stream);
+    if (int e = norm_check("norm_head_fwd", dtype, Nb, V, HC, G)) return e;
+    long long blocks = (V + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    dim3 grid((int)blocks, Nb);
+    DYCON_DISPATCH(dtype, {
+        DYCON_HEAD_K(classes, norm_apply_headc_kernel<T, HK><<<grid, 256, 0, stream>>>((const T*)x, V, G, stats, gamma, beta, relu, chan_scale,
+                                                                                      head_w, head_b, logits));
+    });
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_norm_headc_bwd(const void* x, const float* g_logits, void* gx, int dtype, int Nb, long long V, int G, int classes,
+                                    const float* stats, const float* gamma, const float* beta, int relu, const float* chan_scale,
+                                    const float* head_w, float* dgamma, float* dbeta, float* workspace, size_t ws_bytes,
+                                    dycon_stream_t stream) {
+    DYCON_REQUIRE(x && g_logits && gx && stats && head_w && workspace, "norm_head_bwd: null pointer");
+    if (int e = head_check("norm_head_bwd", classes)) return e;
+    if (classes == 2)
+        return dycon_norm_head_bwd(x, g_logits, gx, dtype, Nb, V, G, stats, gamma, beta, relu, chan_scale, head_w, dgamma, dbeta, workspace,
+                                   ws_bytes, stream);
+    if (int e = norm_check("norm_head_bwd", dtype, Nb, V, HC, G)) return e;
+    DYCON_REQUIRE(ws_bytes >= dycon_norm_headc_workspace(Nb, V, classes), "norm_head_bwd: workspace too small");
+    const NormPlan p = norm_plan(V);
+    float* ab = workspace + (size_t)Nb * p.chunks * HC * 2;
+    float* hpart = workspace + dycon_norm_workspace(Nb, V, HC) / sizeof(float);
+    dim3 grid(p.chunks, Nb);
+    DYCON_DISPATCH(dtype, {
+        DYCON_HEAD_K(classes, norm_head_partialc_kernel<T, HK><<<grid, 256, 0, stream>>>((const T*)x, g_logits, workspace, hpart, V, G,
+                                                                                        p.rows_per_chunk, stats, gamma, beta, relu,
+                                                                                        chan_scale, head_w));
+    });
+    DYCON_LAUNCH_CHECK();
+    const int nfin = Nb * G + ((dgamma || dbeta) ? HC : 0);
+    norm_finalize_bwd_kernel<<<nfin, 256, 0, stream>>>(workspace, Nb, p.chunks, HC, G, gamma, ab, dgamma, dbeta);
+    DYCON_LAUNCH_CHECK();
+    DYCON_DISPATCH(dtype, {
+        dim3 grid2(apply_grid(V, HC, Vec16<T>::N), Nb);
+        DYCON_HEAD_K(classes, norm_head_bwd_applyc_kernel<T, HK><<<grid2, 256, 0, stream>>>((const T*)x, g_logits, (T*)gx, V, G, stats,
+                                                                                           gamma, beta, ab, relu, chan_scale, head_w));
+    });
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+// the head's weight / bias gradient from the partials dycon_norm_headc_bwd left in its workspace (a tiny launch the caller may put
+// on another stream: nothing on the data-gradient chain depends on it)
+extern "C" int dycon_norm_headc_dparams(const float* workspace, int Nb, long long V, int classes, float* d_head_w, float* d_head_b,
+                                        dycon_stream_t stream) {
+    DYCON_REQUIRE(workspace && (d_head_w || d_head_b), "norm_head_dparams: bad arguments");
+    if (int e = head_check("norm_head_dparams", classes)) return e;
+    if (classes == 2) return dycon_norm_head_dparams(workspace, Nb, V, d_head_w, d_head_b, stream);
+    const NormPlan p = norm_plan(V);
+    const float* hpart = workspace + dycon_norm_workspace(Nb, V, HC) / sizeof(float);
+    norm_headc_finalize_kernel<<<hpart_len(classes), 256, 0, stream>>>(hpart, Nb * p.chunks, classes, d_head_w, d_head_b);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+constexpr int HK2 = 2;                              // the DyCON step's two logits
+constexpr int HPART2 = HK2 * HC + HK2;              // per-chunk head partials: dW[k][c], db[k]
+
+
+template <typename T>
+__global__ __launch_bounds__(256) void norm_apply_head_kernel(const T* __restrict__ X, long long V, int G,
+                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, int relu,
+                                                              const float* __restrict__ chan_scale, const float* __restrict__ W,
+                                                              const float* __restrict__ hb, float* __restrict__ L) {
+    constexpr int VN = Vec16<T>::N;
+    __shared__ float ss[3 * HC + HK2 * HC + HK2];
+    const int n = blockIdx.y, cpg = HC / G;
+    if (threadIdx.x < HC) {
+        const int c = threadIdx.x, g = c / cpg;
+        const float mean = stats[((long long)n * G + g) * 2], rstd = stats[((long long)n * G + g) * 2 + 1];
+        const float gm = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+        ss[c] = rstd * gm;
+        ss[HC + c] = bt - mean * rstd * gm;
+        ss[2 * HC + c] = chan_scale ? chan_scale[(long long)n * HC + c] : 1.f;
+    }
+    if (threadIdx.x < HK2 * HC) ss[3 * HC + threadIdx.x] = W[threadIdx.x];
+    if (threadIdx.x < HK2) ss[3 * HC + HK2 * HC + threadIdx.x] = hb ? hb[threadIdx.x] : 0.f;
+    __syncthreads();
     float sc[HC], sh[HC], dr[HC], w0[HC], w1[HC];
 #pragma unroll
     for (int c = 0; c < HC; ++c) { sc[c] = ss[c]; sh[c] = ss[HC + c]; dr[c] = ss[2 * HC + c]; w0[c] = ss[3 * HC + c]; w1[c] = ss[4 * HC + c]; }
-    const float b0 = ss[3 * HC + HK * HC], b1 = ss[3 * HC + HK * HC + 1];
+    const float b0 = ss[3 * HC + HK2 * HC], b1 = ss[3 * HC + HK2 * HC + 1];
     const T* xp = X + (long long)n * V * HC;
     float2* lp = reinterpret_cast<float2*>(L) + (long long)n * V;
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
@@ -932,7 +1320,7 @@ __global__ __launch_bounds__(256) void norm_apply_head_kernel(const T* __restric
 }
 
 // statistics pass of the backward: thread mapping, row order and summation order of norm_partial_kernel<T, 1>, with gy formed on the fly;
-// additionally the head's weight / bias gradient partials of the chunk (hpart[(n, chunk)][HPART])
+// additionally the head's weight / bias gradient partials of the chunk (hpart[(n, chunk)][HPART2])
 template <typename T>
 __global__ __launch_bounds__(256) void norm_head_partial_kernel(const T* __restrict__ S, const float* __restrict__ GL,
                                                                 float* __restrict__ part, float* __restrict__ hpart, long long V,
@@ -943,7 +1331,7 @@ __global__ __launch_bounds__(256) void norm_head_partial_kernel(const T* __restr
     constexpr int VN = Vec16<T>::N;
     constexpr int NGRP = HC / VN, RPI = 256 / NGRP;
     __shared__ float sm[4][256][VN + 1];
-    __shared__ float sb[256][HK];
+    __shared__ float sb[256][HK2];
     const int n = blockIdx.y, chunk = blockIdx.x;
     const int cg = threadIdx.x % NGRP, rr = threadIdx.x / NGRP;
     const long long v0 = chunk * rows_per_chunk, v1 = min(V, v0 + rows_per_chunk);
@@ -1002,29 +1390,29 @@ __global__ __launch_bounds__(256) void norm_head_partial_kernel(const T* __restr
         float* d = part + ((((long long)n * gridDim.x + chunk) * HC) + o) * 2;
         d[0] = s0;
         d[1] = s1;
-    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + HK * HC) {
+    } else if (threadIdx.x >= 64 && threadIdx.x < 64 + HK2 * HC) {
         const int j = threadIdx.x - 64, kk = j / HC, o = j % HC, og = o / VN, ok = o % VN;
         float s0 = 0.f;
         for (int q = 0; q < RPI; ++q) s0 += sm[2 + kk][q * NGRP + og][ok];
-        hpart[((long long)n * gridDim.x + chunk) * HPART + j] = s0;
-    } else if (threadIdx.x >= 128 && threadIdx.x < 128 + HK) {
+        hpart[((long long)n * gridDim.x + chunk) * HPART2 + j] = s0;
+    } else if (threadIdx.x >= 128 && threadIdx.x < 128 + HK2) {
         const int kk = threadIdx.x - 128;
         float s0 = 0.f;
         for (int q = 0; q < 256; ++q) s0 += sb[q][kk];
-        hpart[((long long)n * gridDim.x + chunk) * HPART + HK * HC + kk] = s0;
+        hpart[((long long)n * gridDim.x + chunk) * HPART2 + HK2 * HC + kk] = s0;
     }
 }
 
-// sums of the head partials over all (n, chunk): one workgroup per output (HPART of them)
+// sums of the head partials over all (n, chunk): one workgroup per output (HPART2 of them)
 __global__ __launch_bounds__(256) void norm_head_finalize_kernel(const float* __restrict__ hpart, int items, float* __restrict__ dW,
                                                                  float* __restrict__ db) {
     const int j = blockIdx.x;
     double s0 = 0.0, s1 = 0.0;
-    for (int e = threadIdx.x; e < items; e += 256) s0 += hpart[(long long)e * HPART + j];
+    for (int e = threadIdx.x; e < items; e += 256) s0 += hpart[(long long)e * HPART2 + j];
     block_sum2_double(s0, s1);
     if (threadIdx.x == 0) {
-        if (j < HK * HC) { if (dW) dW[j] = (float)s0; }
-        else if (db) db[j - HK * HC] = (float)s0;
+        if (j < HK2 * HC) { if (dW) dW[j] = (float)s0; }
+        else if (db) db[j - HK2 * HC] = (float)s0;
     }
 }
 
@@ -1078,7 +1466,7 @@ __global__ __launch_bounds__(256) void norm_head_bwd_apply_kernel(const T* __res
 
 extern "C" size_t dycon_norm_head_workspace(int Nb, long long V) {
     const NormPlan p = norm_plan(V);
-    return dycon_norm_workspace(Nb, V, HC) + (size_t)Nb * p.chunks * HPART * sizeof(float);
+    return dycon_norm_workspace(Nb, V, HC) + (size_t)Nb * p.chunks * HPART2 * sizeof(float);
 }
 
 extern "C" int dycon_norm_head_fwd(const void* x, int dtype, int Nb, long long V, int G, const float* stats, const float* gamma,
@@ -1131,7 +1519,7 @@ extern "C" int dycon_norm_head_dparams(const float* workspace, int Nb, long long
     DYCON_REQUIRE(workspace && (d_head_w || d_head_b), "norm_head_dparams: bad arguments");
     const NormPlan p = norm_plan(V);
     const float* hpart = workspace + dycon_norm_workspace(Nb, V, HC) / sizeof(float);
-    norm_head_finalize_kernel<<<HPART, 256, 0, stream>>>(hpart, Nb * p.chunks, d_head_w, d_head_b);
+    norm_head_finalize_kernel<<<HPART2, 256, 0, stream>>>(hpart, Nb * p.chunks, d_head_w, d_head_b);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }

@@ -781,3 +781,92 @@ extern "C" int dycon_focal_bwd(const dycon_view_t* x, const void* target, int ta
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }
+
+// ------------------------------------------------------------------ UnCLoss for C classes (code/utils/dycon_losses.py:94-118)
+// Per voxel: p = softmax(s), q = softmax(t), H = -sum_c p_c log(p_c + 1e-6),
+//   l = sum_c (p_c - q_c)^2 / (e^{beta H_s} + e^{beta H_t}) + beta (H_s + H_t);      the loss is the mean of l over n V voxels.
+// (The 2-class loss of the DyCON step lives in losses.hip, fused with the step's other voxel losses.)
+__device__ __forceinline__ float uncl_probs(const View& a, long long n, long long v, int C, float* p) {
+    // p = softmax over the C channels (exp(x - max) / sum, as torch); returns H
+    const float* base = a.p + n * a.sn + v * a.sv;
+    float x[MAXC], m = -INFINITY, z = 0.f, H = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) { x[c] = base[c * a.sc]; m = fmaxf(m, x[c]); }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) { p[c] = expf(x[c] - m); z += p[c]; }
+#pragma unroll
+    for (int c = 0; c < MAXC; ++c)
+        if (c < C) { p[c] = p[c] / z; H -= p[c] * logf(p[c] + 1e-6f); }
+    return H;
+}
+
+__global__ __launch_bounds__(256) void uncl_fwd_kernel(View s, View t, long long n_, int C, long long V, float beta,
+                                                       double* __restrict__ sum) {
+    const long long total = n_ * V;
+    float acc = 0.f;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / V, v = i - n * V;
+        float p[MAXC], q[MAXC];
+        const float Hs = uncl_probs(s, n, v, C, p), Ht = uncl_probs(t, n, v, C, q);
+        float d2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) { const float d = p[c] - q[c]; d2 += d * d; }
+        acc += d2 / (expf(beta * Hs) + expf(beta * Ht)) + beta * (Hs + Ht);
+    }
+    block_atomic_double(acc, sum);
+}
+
+// gradient w.r.t. the student logits: dl/dp_c = 2 (p_c - q_c) / D + beta (1 - d2 e^{beta H_s} / D^2) dH_s/dp_c with
+// D = e^{beta H_s} + e^{beta H_t}, dH_s/dp_c = -(log(p_c + 1e-6) + p_c / (p_c + 1e-6)); then through the softmax
+__global__ __launch_bounds__(256) void uncl_bwd_kernel(View s, View t, long long n_, int C, long long V, float beta,
+                                                       const float* __restrict__ g_up, float* __restrict__ gr, long long osn,
+                                                       long long osc, long long osv) {
+    const long long total = n_ * V;
+    const float k = (float)((double)g_up[0] / (double)total);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long n = i / V, v = i - n * V;
+        float p[MAXC], q[MAXC], h[MAXC];
+        const float Hs = uncl_probs(s, n, v, C, p), Ht = uncl_probs(t, n, v, C, q);
+        float d2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) { const float d = p[c] - q[c]; d2 += d * d; }
+        const float es = expf(beta * Hs), D = es + expf(beta * Ht);
+        const float gH = beta * (1.f - d2 * es / (D * D));
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) {
+                const float pe = p[c] + 1e-6f;
+                h[c] = 2.f * (p[c] - q[c]) / D - gH * (logf(pe) + p[c] / pe);
+                dot += h[c] * p[c];
+            }
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+            if (c < C) gr[n * osn + c * osc + v * osv] = k * (p[c] * (h[c] - dot));
+    }
+}
+
+extern "C" int dycon_uncl_fwd(const dycon_view_t* s, const dycon_view_t* t, long long n, int C, long long V, float beta, double* sum,
+                              float* out, dycon_stream_t stream) {
+    CHECK_VIEW(s); CHECK_VIEW(t); CHECK_DIMS();
+    DYCON_REQUIRE(sum && out && n * V > 0, "uncl_fwd: bad arguments (mean of an empty input?)");
+    if (!zero_doubles(sum, 1, stream)) return DYCON_ERR_LAUNCH;
+    uncl_fwd_kernel<<<grid_for(n * V), 256, 0, stream>>>(mkview(s), mkview(t), n, C, V, beta, sum);
+    scalar_mean_kernel<<<1, 1, 0, stream>>>(sum, (double)n * V, out);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_uncl_bwd(const dycon_view_t* s, const dycon_view_t* t, long long n, int C, long long V, float beta,
+                              const float* g_up, const dycon_view_t* grad, dycon_stream_t stream) {
+    CHECK_VIEW(s); CHECK_VIEW(t); CHECK_VIEW(grad); CHECK_DIMS();
+    DYCON_REQUIRE(g_up && n * V > 0, "uncl_bwd: bad arguments");
+    uncl_bwd_kernel<<<grid_for(n * V), 256, 0, stream>>>(mkview(s), mkview(t), n, C, V, beta, g_up, (float*)grad->p, grad->sn, grad->sc,
+                                                         grad->sv);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}

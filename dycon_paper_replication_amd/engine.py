@@ -641,7 +641,7 @@ class Engine:
                 db = self.g[prefix + ".bias"] if beta is not None else None
                 gz, pend = ops.norm_head_bwd(z, gl, stats, Nb, V, G, hw, gamma, beta, True, dg, db, chan_scale)
                 gw, gb = self.g[head + ".weight"], self.g[head + ".bias"]
-                if self.wgrad_stream is not None:      # the head's 2 x 16 weight gradient: a sum of per-chunk partials, off the chain
+                if self.wgrad_stream is not None:      # the head's K x 16 weight gradient: a sum of per-chunk partials, off the chain
                     ops.fork(ops.cur_stream(), self.wgrad_stream)
                     with ops.on_stream(self.wgrad_stream, light=True):
                         ops.norm_head_dparams(pend, gw, gb)
@@ -919,7 +919,7 @@ class Engine:
         u = up("block_seven_up", block("block_seven", u, 3), x2)
         u = up("block_eight_up", block("block_eight", u, 2), x1)
         w9, wo = self.p["block_nine.conv.0.weight"], self.p["out_conv.weight"]
-        head_ok = w9.shape[0] == 16 and wo.shape[0] == 2           # the fused kernels are written for 16 channels -> 2 classes
+        head_ok = w9.shape[0] == 16 and 1 <= wo.shape[0] <= 8     # the fused kernels are written for 16 channels -> 1..8 classes
         bn_drop = nk == "bn" and self.dropout.mode != "off"        # per-sample Dropout3d masks under BatchNorm: unfused (see _norm)
         if nk != "none" and head_ok and not bn_drop:   # block_nine's norm + ReLU + Dropout3d + out_conv in one pass
             z9 = self._conv("block_nine.conv.0", u, "k3", norm_groups=ngroups(u, "block_nine.conv.0"))
@@ -984,7 +984,7 @@ class Engine:
     # ---------------------------------------------------------------- public
     def forward(self, x, training=True, record=True, dropout: Optional[DropoutSpec] = None, update_bn=True,
                 want_sdf=False):
-        """x: (B, D, H, W, Cin) fp32 or ``dtype``.  Returns (logits fp32 (B,D,H,W,2), feats (B,d,h,w,256), sdf|None)."""
+        """x: (B, D, H, W, Cin) fp32 or ``dtype``.  Returns (logits fp32 (B,D,H,W,classes), feats (B,d,h,w,256), sdf|None)."""
         assert x.dim() == 5 and x.is_contiguous()
         self.recording = bool(record)
         self.update_bn = update_bn

@@ -88,8 +88,8 @@ class HipSegNet(nn.Module):
     def __init__(self, in_channels=1, n_classes=2, scale_factor=2, normalization="groupnorm", has_dropout=True,
                  dtype=torch.float32, seed=None, use_aspp=False):
         super().__init__()
-        if n_classes != 2:
-            raise NotImplementedError("the DyCON step hard-codes 2 classes (train_DyCON_BraTS19.py:146)")
+        if not 1 <= int(n_classes) <= 8:      # the head kernels' widths (csrc/norm.hip, csrc/conv.hip); the reference takes any class_num
+            raise ValueError(f"n_classes must be in 1..8, got {n_classes}")
         self.in_channels, self.n_classes, self.scale_factor = in_channels, n_classes, scale_factor
         self.normalization, self.has_dropout, self.compute_dtype = normalization, has_dropout, dtype
         self.use_aspp = bool(use_aspp)

@@ -477,29 +477,43 @@ def norm_bwd(src, from_y, gy, stats, Nb, V, C, G, gamma=None, beta=None, relu=Tr
 
 
 def norm_head_fwd(x, stats, Nb, V, G, head_w, head_b, gamma=None, beta=None, relu=True, chan_scale=None):
-    """the 2-class head fused into the last normalisation (16 channels): logits (Nb, D, H, W, 2) fp32 straight from the pre-norm tensor"""
-    logits = torch.empty(x.shape[:-1] + (2,), dtype=torch.float32, device=x.device)
+    """the class head fused into the last normalisation (16 channels): logits (Nb, D, H, W, K) fp32 straight from the pre-norm tensor.
+    K = head_w.shape[0] classes, 1..8; K = 2 takes the 2-class entry points (the DyCON step's launches), other K dycon_norm_headc_*"""
+    K = head_w.shape[0]
+    logits = torch.empty(x.shape[:-1] + (K,), dtype=torch.float32, device=x.device)
     with _Region("norm_fwd", x.numel() * _es(x) + logits.numel() * 4, 8 * x.numel()):
-        call("dycon_norm_head_fwd", _p(x), dt(x), Nb, V, G, _p(stats), _p(gamma), _p(beta), int(relu), _p(chan_scale), _p(head_w),
-             _p(head_b), _p(logits), _s())
+        if K == 2:
+            call("dycon_norm_head_fwd", _p(x), dt(x), Nb, V, G, _p(stats), _p(gamma), _p(beta), int(relu), _p(chan_scale), _p(head_w),
+                 _p(head_b), _p(logits), _s())
+        else:
+            call("dycon_norm_headc_fwd", _p(x), dt(x), Nb, V, G, K, _p(stats), _p(gamma), _p(beta), int(relu), _p(chan_scale),
+                 _p(head_w), _p(head_b), _p(logits), _s())
     return logits
 
 
 def norm_head_bwd(x, g_logits, stats, Nb, V, G, head_w, gamma=None, beta=None, relu=True, dgamma=None, dbeta=None, chan_scale=None):
     """returns (gx, pending): pending -> norm_head_dparams(pending, d_head_w, d_head_b) on any stream"""
+    K = head_w.shape[0]
     gx = torch.empty_like(x)
-    ws = _ws(query("dycon_norm_head_workspace", Nb, V), x)
+    ws = _ws(query("dycon_norm_head_workspace", Nb, V) if K == 2 else query("dycon_norm_headc_workspace", Nb, V, K), x)
     nb = x.numel() * _es(x)
     with _Region("norm_bwd", nb * 3 + g_logits.numel() * 8, 14 * x.numel(),
                  parts=[("partial", nb + g_logits.numel() * 4, 7 * x.numel()), ("apply", 2 * nb + g_logits.numel() * 4, 7 * x.numel())]):
-        call("dycon_norm_head_bwd", _p(x), _p(g_logits), _p(gx), dt(x), Nb, V, G, _p(stats), _p(gamma), _p(beta), int(relu),
-             _p(chan_scale), _p(head_w), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 4, _s())
-    return gx, (ws, Nb, V)
+        if K == 2:
+            call("dycon_norm_head_bwd", _p(x), _p(g_logits), _p(gx), dt(x), Nb, V, G, _p(stats), _p(gamma), _p(beta), int(relu),
+                 _p(chan_scale), _p(head_w), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 4, _s())
+        else:
+            call("dycon_norm_headc_bwd", _p(x), _p(g_logits), _p(gx), dt(x), Nb, V, G, K, _p(stats), _p(gamma), _p(beta), int(relu),
+                 _p(chan_scale), _p(head_w), _p(dgamma), _p(dbeta), _p(ws), ws.numel() * 4, _s())
+    return gx, (ws, Nb, V, K)
 
 
 def norm_head_dparams(pending, d_head_w, d_head_b):
-    ws, Nb, V = pending
-    call("dycon_norm_head_dparams", _p(ws), Nb, V, _p(d_head_w), _p(d_head_b), _s())
+    ws, Nb, V, K = pending
+    if K == 2:
+        call("dycon_norm_head_dparams", _p(ws), Nb, V, _p(d_head_w), _p(d_head_b), _s())
+    else:
+        call("dycon_norm_headc_dparams", _p(ws), Nb, V, K, _p(d_head_w), _p(d_head_b), _s())
 
 
 def norm_bwd_stats(src, gy, stats, Nb, V, C, G, gamma=None, beta=None, relu=True, dgamma=None, dbeta=None, chan_scale=None):

@@ -11,7 +11,7 @@ import math
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 
 
 def adaptive_beta(epoch, total_epochs, max_beta=5.0, min_beta=0.5):
@@ -60,6 +60,8 @@ def _ndhwc_logits(x):
 
 
 class _UnCLFunction(torch.autograd.Function):
+    """2 classes: the fused voxel-loss kernels of the DyCON step (csrc/losses.hip)."""
+
     @staticmethod
     def forward(ctx, s_logits, t_logits, beta):
         s, t = _ndhwc_logits(s_logits), _ndhwc_logits(t_logits)
@@ -81,11 +83,44 @@ class _UnCLFunction(torch.autograd.Function):
         return gs.permute(0, 4, 1, 2, 3), None, None
 
 
+class _UnCLClassesFunction(torch.autograd.Function):
+    """Any other class count in 1..8: dycon_uncl_fwd / _bwd (csrc/reflosses.hip) over strided (n, C, V) views -- an NCDHW tensor and
+    the nets' channels-last views are read in place; the gradient is written in the student logits' own layout."""
+
+    @staticmethod
+    def forward(ctx, s_logits, t_logits, beta):
+        from .losses import _f32, _ref, _scratch, _view_ncv
+        s, vs, n, C, V = _view_ncv(_f32(s_logits))
+        t, vt, _, _, _ = _view_ncv(_f32(t_logits))
+        sum_, out = _scratch(s.device)
+        _lib.call("dycon_uncl_fwd", _ref(vs), _ref(vt), n, C, V, beta, sum_.data_ptr(), out.data_ptr(), ops._s())
+        ctx.save_for_backward(s, t)
+        ctx.beta, ctx.in_dtype = beta, s_logits.dtype
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        from .losses import _f32, _ref, _view_ncv
+        s, t = ctx.saved_tensors
+        _, vs, n, C, V = _view_ncv(s)
+        _, vt, _, _, _ = _view_ncv(t)
+        gu = _f32(g).reshape(1).contiguous()
+        gs = torch.empty_like(s)                  # preserves the strides of a dense (permuted) tensor
+        gs, vg, _, _, _ = _view_ncv(gs)
+        _lib.call("dycon_uncl_bwd", _ref(vs), _ref(vt), n, C, V, ctx.beta, gu.data_ptr(), _ref(vg), ops._s())
+        return gs.to(ctx.in_dtype), None, None
+
+
 class UnCLoss(nn.Module):
-    """Uncertainty-weighted consistency (dycon_losses.py:50-118): forward(s_logits, t_logits, beta) -> 0-dim."""
+    """Uncertainty-weighted consistency (dycon_losses.py:50-118): forward(s_logits, t_logits, beta) -> 0-dim.
+    (B, C, D, H, W) logits with C in 1..8; softmax and entropy over dim 1, as the reference."""
 
     def forward(self, s_logits, t_logits, beta):
-        return _UnCLFunction.apply(s_logits, t_logits.detach(), float(beta))
+        if s_logits.dim() != 5 or not 1 <= s_logits.shape[1] <= 8 or s_logits.shape != t_logits.shape:
+            raise ValueError(f"UnCLoss: expected two (B,C,D,H,W) logit tensors with C in 1..8, got {tuple(s_logits.shape)} "
+                             f"and {tuple(t_logits.shape)}")
+        fn = _UnCLFunction if s_logits.shape[1] == 2 else _UnCLClassesFunction
+        return fn.apply(s_logits, t_logits.detach(), float(beta))
 
 
 class _FeCLFunction(torch.autograd.Function):

@@ -204,6 +204,21 @@ int dycon_norm_head_bwd(const void* x, const float* g_logits, void* gx, int dtyp
                         dycon_stream_t stream);
 int dycon_norm_head_dparams(const float* workspace, int Nb, long long V, float* d_head_w, float* d_head_b,
                             dycon_stream_t stream);
+/* The same head for `classes` logits, 1..8 (net_factory_3d's class_num): logits / g_logits are (Nb, V, classes) fp32 rows,
+ * head_w = out_conv.weight (classes,16,1,1,1), head_b = out_conv.bias.  Per voxel o_k = b_k, then o_k += y_c W[k][c] for c = 0..15;
+ * gy_c = sum over k in order of g_k W[k][c], rounded to the storage type: the arithmetic of the launches the fusion replaces, so
+ * the logits are theirs bit for bit.  classes = 2 is handed to the entry points above (same kernels, same bits).  The workspace holds classes * 17 head partials per
+ * (sample, chunk) behind the normalisation's own. */
+size_t dycon_norm_headc_workspace(int Nb, long long V, int classes);
+int dycon_norm_headc_fwd(const void* x, int dtype, int Nb, long long V, int G, int classes, const float* stats,
+                         const float* gamma, const float* beta, int relu, const float* chan_scale, const float* head_w,
+                         const float* head_b, float* logits, dycon_stream_t stream);
+int dycon_norm_headc_bwd(const void* x, const float* g_logits, void* gx, int dtype, int Nb, long long V, int G, int classes,
+                         const float* stats, const float* gamma, const float* beta, int relu, const float* chan_scale,
+                         const float* head_w, float* dgamma, float* dbeta, float* workspace, size_t ws_bytes,
+                         dycon_stream_t stream);
+int dycon_norm_headc_dparams(const float* workspace, int Nb, long long V, int classes, float* d_head_w, float* d_head_b,
+                             dycon_stream_t stream);
 /* The normalisation after the FIRST convolution (block_one, VNet.py:176) has one consumer of its data gradient: that convolution's
  * weight gradient (the image needs none).  So the gradient is never stored:
  *   dycon_norm_bwd_stats     = the first two launches of dycon_norm_bwd (statistics pass + finalize): dgamma / dbeta, and the per-group
@@ -428,6 +443,14 @@ int dycon_focal_fwd(const dycon_view_t* x, const void* target, int target_kind, 
 /* grad = g_up[0] * d out / d x with pt held constant, as the reference detaches it (utils/losses.py:141) */
 int dycon_focal_bwd(const dycon_view_t* x, const void* target, int target_kind, long long n, int C, long long V, float gamma,
                     const float* alpha_host, int size_average, const float* g_up, const dycon_view_t* grad, dycon_stream_t stream);
+/* dycon_losses.UnCLoss()(s, t, beta) for C classes (utils/dycon_losses.py:94-118): out[0] = mean over the n V voxels of
+ * sum_c (p_c - q_c)^2 / (e^{beta H_s} + e^{beta H_t}) + beta (H_s + H_t), p = softmax(s, 1), q = softmax(t, 1),
+ * H = -sum_c p_c log(p_c + 1e-6).  sum: one double of scratch.  (The DyCON step's 2-class UnCL is part of dycon_seg_losses_*.) */
+int dycon_uncl_fwd(const dycon_view_t* s, const dycon_view_t* t, long long n, int C, long long V, float beta, double* sum, float* out,
+                   dycon_stream_t stream);
+/* grad = g_up[0] * d out / d s (the teacher logits t are constants) */
+int dycon_uncl_bwd(const dycon_view_t* s, const dycon_view_t* t, long long n, int C, long long V, float beta, const float* g_up,
+                   const dycon_view_t* grad, dycon_stream_t stream);
 
 /* rows of (R, C): y = x / max(||x||, eps)   (F.normalize, train_DyCON_BraTS19.py:316-323) */
 int dycon_l2norm_fwd(const void* x, void* y, float* norms, int dtype, long long R, int C, float eps,
@@ -511,6 +534,9 @@ int dycon_nonfinite_flag(const float* x, int* flag, dycon_stream_t stream);
  * deterministic although windows overlap. */
 int dycon_sw_accumulate(const float* logits, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                         float* score, float* cnt, int D0, int D1, int D2, dycon_stream_t stream);
+/* the same for a C-class model, C in 2..8: logits (n_patches, p0, p1, p2, C) fp32; adds softmax(logits)[1] of the C-way softmax */
+int dycon_sw_accumulate_c(const float* logits, int C, int n_patches, int p0, int p1, int p2, const int* origins_dev,
+                          float* score, float* cnt, int D0, int D1, int D2, dycon_stream_t stream);
 /* prob = score / cnt (may be NULL), label = prob > thresh   (:344-345) */
 int dycon_sw_finalize(const float* score, const float* cnt, long long n, float thresh, uint8_t* label,
                       float* prob, dycon_stream_t stream);

@@ -1,0 +1,160 @@
+"""CPU: class counts other than 2 (net_factory_3d(class_num=C), UnCLoss, the evaluator) -- the contract around the kernels:
+state-dict names / shapes against the names recorded from the reference, argument guards, the C ABI surface, the host-side
+workspace / plan queries, and the self-consistency of the fixtures tests/golden/make_golden_nclasses.py wrote."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+
+from dycon_paper_replication_amd import _lib
+from dycon_paper_replication_amd._lib import BF16, CONV_1X1, F32
+from dycon_paper_replication_amd.engine import param_spec
+from dycon_paper_replication_amd.networks.net_factory_3d import net_factory_3d
+from dycon_paper_replication_amd.networks._base import HipSegNet
+from dycon_paper_replication_amd.utils import dycon_losses
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_ENTRY_POINTS = ("dycon_norm_headc_workspace", "dycon_norm_headc_fwd", "dycon_norm_headc_bwd", "dycon_norm_headc_dparams",
+                    "dycon_uncl_fwd", "dycon_uncl_bwd", "dycon_sw_accumulate_c")
+
+
+@pytest.mark.parametrize("tag,net_type,C", [("vnet1", "vnet", 1), ("vnet3", "vnet", 3), ("unet3", "unet_3D", 3), ("vnet8", "vnet", 8)])
+def test_state_dict_contract_per_class_count(tag, net_type, C):
+    """parameter names, order and shapes of the module equal the reference modules' for this class count"""
+    g = load_golden("full_nets_nc")
+    ref_names = list(g[f"{tag}.param_names"])
+    ref_shapes = [tuple(int(d) for d in s.split(";")) for s in g[f"{tag}.param_shapes"]]
+    spec = param_spec(net_type, 1, C)
+    assert list(spec) == ref_names
+    assert [tuple(s) for s in spec.values()] == ref_shapes
+    net = net_factory_3d(net_type, 1, C, 2)
+    named = list(net.named_parameters())
+    assert [k for k, _ in named] == ref_names
+    assert [tuple(p.shape) for _, p in named] == ref_shapes
+    head = "out_conv" if net_type == "vnet" else "out_conv2"
+    assert tuple(net.state_dict()[head + ".weight"].shape) == (C, 16, 1, 1, 1) and tuple(net.state_dict()[head + ".bias"].shape) == (C,)
+
+
+@pytest.mark.parametrize("C", [0, 9, -1])
+def test_class_count_outside_1_to_8_is_refused(C):
+    with pytest.raises(ValueError, match="1..8"):
+        net_factory_3d("vnet", 1, C, 2)
+    with pytest.raises(ValueError, match="1..8"):
+        net_factory_3d("unet_3D", 1, C, 2)
+
+    class Net(HipSegNet):
+        net_type = "vnet"
+    with pytest.raises(ValueError, match="1..8"):
+        Net(n_classes=C)
+
+
+@pytest.mark.parametrize("C", [1, 3, 4, 5, 6, 7, 8])
+def test_every_class_count_in_range_builds(C):
+    assert net_factory_3d("vnet", 1, C, 2).n_classes == C
+
+
+def test_uncl_refuses_bad_shapes():
+    crit = dycon_losses.UnCLoss()
+    with pytest.raises(ValueError, match="1..8"):
+        crit(torch.zeros(1, 9, 2, 2, 2), torch.zeros(1, 9, 2, 2, 2), 1.0)
+    with pytest.raises(ValueError):
+        crit(torch.zeros(1, 3, 2, 2, 2), torch.zeros(1, 4, 2, 2, 2), 1.0)
+    with pytest.raises(ValueError):
+        crit(torch.zeros(3, 8, 8), torch.zeros(3, 8, 8), 1.0)
+
+
+def test_new_entry_points_declared_exported_and_bound():
+    hdr = open(os.path.join(ROOT, "include", "dycon_hip.h")).read()
+    declared = set(re.findall(r"\b(dycon_[a-z0-9_]+)\s*\(", hdr))
+    vmap = open(os.path.join(ROOT, "dycon_paper_replication_amd", "csrc", "exports.map")).read()
+    assert re.search(r"global:\s*dycon_\*;", vmap)                    # the version script exports the dycon_ prefix
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    lib = _lib.load()
+    for name in NEW_ENTRY_POINTS:
+        assert name in declared, name
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(raw, name) and getattr(lib, name).argtypes is not None, name
+
+
+def test_head_workspace_grows_with_the_class_count():
+    """the workspace of the fused head = the normalisation's own + (classes * 16 + classes) floats per (sample, chunk)"""
+    lib = _lib.load()
+    for Nb, V in ((3, 20 * 18 * 16), (4, 96 ** 3), (1, 5 * 7 * 9)):
+        base = lib.dycon_norm_workspace(Nb, V, 16)
+        sizes = [lib.dycon_norm_headc_workspace(Nb, V, C) for C in range(1, 9)]
+        per_class = sizes[0] - base
+        assert per_class > 0 and per_class % (Nb * 17 * 4) == 0           # Nb * chunks * 17 floats
+        assert sizes == [base + C * per_class for C in range(1, 9)]
+        assert sizes[1] == lib.dycon_norm_head_workspace(Nb, V)           # the 2-class query is the same plan
+    assert lib.dycon_norm_headc_workspace(2, 4096, 0) == 0 and lib.dycon_norm_headc_workspace(2, 4096, 9) == 0
+
+
+def test_skinny_wgrad_plans_for_1_to_8_classes():
+    lib = _lib.load()
+    name = lambda xd, gd, C: lib.dycon_conv_wgrad_name(xd, gd, CONV_1X1, 2, 12, 12, 8, 16, C).decode()  # noqa: E731
+    for C in range(1, 9):
+        assert name(BF16, F32, C) == "wgrad_1x1_skinny" and name(F32, F32, C) == "wgrad_1x1_skinny", C
+        assert name(F32, BF16, C) == "conv_wgrad_direct"                  # fp32 gradients only
+    assert name(BF16, F32, 9) == "conv_wgrad_direct"
+
+
+def _uncl_restated(s, t, beta):
+    """the reference's UnCLoss.forward (utils/dycon_losses.py:94-118) in torch"""
+    p_s, p_t = torch.softmax(s, 1), torch.softmax(t, 1)
+    H_s = -torch.sum(p_s * torch.log(p_s + 1e-6), 1, keepdim=True)
+    H_t = -torch.sum(p_t * torch.log(p_t + 1e-6), 1, keepdim=True)
+    loss = (p_s - p_t) ** 2 / (torch.exp(beta * H_s) + torch.exp(beta * H_t))
+    return torch.mean(loss.sum(1) + beta * (H_s + H_t)).mean()
+
+
+def test_uncl_fixture_is_self_consistent():
+    g = load_golden("uncl_nc")
+    assert list(g["classes"]) == [1, 3, 4, 8] and list(g["betas"]) == [0.5, 2.0, 5.0]
+    for C in g["classes"]:
+        for tag in (f"c{C}", f"c{C}_big"):
+            s, t = torch.from_numpy(g[f"{tag}.s"]), torch.from_numpy(g[f"{tag}.t"])
+            assert tuple(s.shape) == (2, C, 6, 5, 7)
+            if tag.endswith("_big"):
+                assert float(s.abs().max()) == 30.0 and float(t.abs().max()) == 30.0
+            for i, beta in enumerate(g["betas"]):
+                for dt, sfx, tol in ((torch.float32, "", 1e-6), (torch.float64, ".f64", 1e-12)):
+                    x = s.to(dt).clone().requires_grad_(True)
+                    loss = _uncl_restated(x, t.to(dt), float(beta))
+                    (gr,) = torch.autograd.grad(loss, x)
+                    np.testing.assert_allclose(loss.item(), g[f"{tag}.loss{i}{sfx}"], rtol=tol)
+                    np.testing.assert_allclose(gr.numpy(), g[f"{tag}.grad{i}{sfx}"], rtol=tol * 100, atol=tol * 1e-2)
+
+
+def test_step_fixture_labels_hold_three_classes():
+    g = load_golden("step_isles_nc3")
+    for kind in ("unet", "vnet"):
+        assert int(g[f"{kind}.classes"]) == 3 and int(g[f"{kind}.LB"]) == 1
+        for step in range(2):
+            lab = g[f"{kind}.s{step}.label"]
+            assert set(np.unique(lab[0])) == {0, 1, 2}       # all three in the labelled sample
+
+
+def test_reference_name_resolves_to_the_class_count_evaluator():
+    """utils.test_3d_patch.test_single_case (the reference's name, which test_all_case and the wrappers call) is the form that takes
+    the class count from the model; it keeps the function written in test_3d_patch.py for 2-class nets"""
+    from dycon_paper_replication_amd.utils import sliding_window, test_3d_patch
+    assert test_3d_patch.test_single_case is sliding_window.test_single_case
+    assert test_3d_patch.test_all_case.__globals__["test_single_case"] is sliding_window.test_single_case
+    two = sliding_window._two_class_single_case
+    assert two is not sliding_window.test_single_case and two.__code__.co_filename.endswith("test_3d_patch.py")
+    calls = []
+    orig, sliding_window._two_class_single_case = two, lambda *a, **k: calls.append((a, k)) or "two-class path"
+    try:
+        net = net_factory_3d("vnet", 1, 2, 2)
+        assert sliding_window.test_single_case(net, np.zeros((32, 32, 16), np.float32), 8, 4, (32, 32, 16), num_classes=2) == "two-class path"
+        assert len(calls) == 1 and calls[0][0][0] is net
+        with pytest.raises(RuntimeError, match="MI355X only"):      # a 3-class net takes the class-count path (which needs the GPU)
+            sliding_window.test_single_case(net_factory_3d("vnet", 1, 3, 2), np.zeros((32, 32, 16), np.float32), 8, 4, (32, 32, 16))
+        assert len(calls) == 1
+    finally:
+        sliding_window._two_class_single_case = orig

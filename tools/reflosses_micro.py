@@ -41,13 +41,57 @@ def timed(fn, warmup, reps):
     return statistics.median(ms), min(ms)
 
 
+def uncl_torch(s_logits, t_logits, beta):
+    """the reference's UnCLoss.forward (utils/dycon_losses.py:94-118) as a torch composition"""
+    p_s, p_t = torch.softmax(s_logits, 1), torch.softmax(t_logits, 1)
+    H_s = -torch.sum(p_s * torch.log(p_s + 1e-6), dim=1, keepdim=True)
+    H_t = -torch.sum(p_t * torch.log(p_t + 1e-6), dim=1, keepdim=True)
+    loss = (p_s - p_t) ** 2 / (torch.exp(beta * H_s) + torch.exp(beta * H_t))
+    return torch.mean(loss.sum(dim=1) + beta * (H_s + H_t)).mean()
+
+
+def uncl_section(a):
+    """--uncl: dycon_losses.UnCLoss at (4, C, 96^3), C in {3, 8}, forward + backward against the torch composition; APPENDED to --out"""
+    from dycon_paper_replication_amd.utils import dycon_losses
+    dev, gen, beta = "cuda:0", torch.Generator().manual_seed(4), 2.0
+    crit = dycon_losses.UnCLoss()
+    lines = [f"# UnCLoss, C classes  {datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%d %H:%M UTC')}  commit {a.commit}",
+             f"# (4, C, 96, 96, 96) fp32 NCDHW, beta {beta}, forward + backward w.r.t. the student logits, median of {a.reps} after "
+             f"{a.warmup} warm-up (min in brackets); alg. GB = student + teacher read twice, gradient written once",
+             f"{'callable':<18}{'HIP ms':>16}{'torch ms':>18}{'speed-up':>10}{'alg. GB':>9}{'GB/s':>8}{'% peak':>8}"]
+    for C in (3, 8):
+        s = (2 * torch.randn(4, C, 96, 96, 96, generator=gen)).to(dev).requires_grad_(True)
+        t = (2 * torch.randn(4, C, 96, 96, 96, generator=gen)).to(dev)
+        gb = 5 * s.numel() * 4 / 1e9
+
+        def run(fn):
+            s.grad = None
+            fn(s, t, beta).backward()
+
+        hip_ms, hip_min = timed(lambda: run(crit), a.warmup, a.reps)
+        th_ms, th_min = timed(lambda: run(uncl_torch), a.warmup, a.reps)
+        gbs = gb / (hip_ms * 1e-3)
+        lines.append(f"{'uncl_c' + str(C):<18}{hip_ms:>8.3f} ({hip_min:.3f}){th_ms:>9.3f} ({th_min:.3f}){th_ms / hip_ms:>9.1f}x{gb:>9.3f}{gbs:>8.0f}"
+                     f"{100 * gbs / HBM_PEAK_GBS:>7.1f}%")
+        del s, t
+        torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if a.out:
+        with open(a.out, "a") as fh:
+            fh.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--commit", default="unknown")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--uncl", action="store_true", help="time UnCLoss for C in {3, 8} only and append to --out")
     a = ap.parse_args()
+    if a.uncl:
+        return uncl_section(a)
     dev = "cuda:0"
     gen = torch.Generator().manual_seed(3)
     shape = (4, 2, 96, 96, 96)
