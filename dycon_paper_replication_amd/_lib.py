@@ -89,6 +89,11 @@ SIGNATURES = {
     "dycon_seg_losses_finalize": (I, [P, I, I, L, F, P, P]),
     "dycon_step_loss": (I, [P, P, F, F, F, I, I, P, P, P]),
     "dycon_step_losses": (I, [P, P, I, I, L, F, C.c_double, F, I, F, F, F, I, I, P, P, P]),
+    "dycon_seg_lossesc_nsums": (I, [I]),
+    "dycon_seg_lossesc_fwd": (I, [P, P, P, I, I, I, L, I, F, I, P, I, P]),
+    "dycon_seg_lossesc_bwd": (I, [P, P, P, I, I, I, L, I, F, P, P, I, P, I, P]),
+    "dycon_seg_lossesc_finalize": (I, [P, I, I, L, I, F, P, P]),
+    "dycon_step_lossesc": (I, [P, P, I, I, L, I, F, C.c_double, F, I, F, F, F, I, I, P, P, P]),
     "dycon_softmax_mse_fwd": (I, [P, P, P, L, I, L, I, P]),
     "dycon_softmax_mse_bwd": (I, [P, P, P, P, L, I, L, I, P]),
     "dycon_softmax_kl_fwd": (I, [P, P, L, I, L, I, P, P, P]),

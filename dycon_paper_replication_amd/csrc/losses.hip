@@ -192,6 +192,270 @@ __global__ void step_losses_kernel(const double* __restrict__ sums, const double
 }
 
 // =================================================================================================
+// voxel losses, C classes (2..8).  logits are (B, V, C) fp32 rows; both rows of a voxel live in registers
+//   sums[5 + 3 C]: 0 ce | 1 mse | 2 kl | 3 uncl_w | 4 uncl_h | 5 + 3 c: I_c, Z_c, Y_c
+// =================================================================================================
+constexpr int SC_CE = 0, SC_MSE = 1, SC_KL = 2, SC_UW = 3, SC_UH = 4, SC_DICE = 5;
+__host__ __device__ constexpr int nsums_c(int classes) { return SC_DICE + 3 * classes; }
+
+// the widest loads the row length allows: 16 B for C % 4 == 0, 8 B for even C, 4 B otherwise (rows are C * 4 bytes apart)
+template <int C> __device__ __forceinline__ void load_row(const float* __restrict__ p, long long i, float (&r)[C]) {
+    const float* q = p + i * C;
+    if constexpr (C % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < C / 4; ++k) {
+            const float4 v = ((const float4*)q)[k];
+            r[4 * k] = v.x; r[4 * k + 1] = v.y; r[4 * k + 2] = v.z; r[4 * k + 3] = v.w;
+        }
+    } else if constexpr (C % 2 == 0) {
+#pragma unroll
+        for (int k = 0; k < C / 2; ++k) {
+            const float2 v = ((const float2*)q)[k];
+            r[2 * k] = v.x; r[2 * k + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < C; ++k) r[k] = q[k];
+    }
+}
+template <int C> __device__ __forceinline__ void store_row(float* __restrict__ p, long long i, const float (&r)[C]) {
+    float* q = p + i * C;
+    if constexpr (C % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < C / 4; ++k) ((float4*)q)[k] = make_float4(r[4 * k], r[4 * k + 1], r[4 * k + 2], r[4 * k + 3]);
+    } else if constexpr (C % 2 == 0) {
+#pragma unroll
+        for (int k = 0; k < C / 2; ++k) ((float2*)q)[k] = make_float2(r[2 * k], r[2 * k + 1]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < C; ++k) q[k] = r[k];
+    }
+}
+
+// p = softmax(l); returns log sum exp(l - m) and m
+template <int C, bool FAST> __device__ __forceinline__ void softmax_c(const float (&l)[C], float (&p)[C], float& lse, float& m) {
+    m = l[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+    float z = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { p[c] = fexp<FAST>(l[c] - m); z += p[c]; }
+    if (FAST) {
+        const float r = __builtin_amdgcn_rcpf(z);
+#pragma unroll
+        for (int c = 0; c < C; ++c) p[c] *= r;
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) p[c] = p[c] / z;
+    }
+    lse = flog<FAST>(z);
+}
+
+// H = -sum_c p_c log(p_c + 1e-6) (utils/dycon_losses.py:99-100)
+template <int C, bool FAST> __device__ __forceinline__ float entropy_c(const float (&p)[C]) {
+    float h = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) h -= p[c] * flog<FAST>(p[c] + 1e-6f);
+    return h;
+}
+
+// cons_kind 0: mse sum only, 1: kl sum only, 2: both (the other slot stays 0)
+template <int C, bool FAST>
+__global__ __launch_bounds__(256) void seg_lossesc_fwd_kernel(const float* __restrict__ SL, const float* __restrict__ TL,
+                                                              const void* __restrict__ labels, int label_bytes, int B, int LB,
+                                                              long long V, float beta, int cons_kind, double* __restrict__ sums) {
+    constexpr int NS = nsums_c(C);
+    __shared__ float red[4][NS];
+    float acc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = 0.f;
+    const long long total = (long long)B * V, lab_end = (long long)LB * V;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        float ls[C], lt[C], ps[C], pt[C];
+        load_row<C>(SL, i, ls);
+        load_row<C>(TL, i, lt);
+        float lse_s, m_s, lse_t, m_t;
+        softmax_c<C, FAST>(ls, ps, lse_s, m_s);
+        softmax_c<C, FAST>(lt, pt, lse_t, m_t);
+        if (i < lab_end) {
+            const int y = load_label(labels, label_bytes, i);
+            float ly = 0.f;      // the label selects by comparison: a value >= C matches nothing and indexes nothing
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float tc = y == c ? 1.f : 0.f;
+                ly += tc * ls[c];
+                acc[SC_DICE + 3 * c] += ps[c] * tc;
+                acc[SC_DICE + 3 * c + 1] += ps[c] * ps[c];
+                acc[SC_DICE + 3 * c + 2] += tc;
+            }
+            acc[SC_CE] += -(ly - m_s - lse_s);
+        } else {
+            // the reference feeds PROBABILITIES to softmax_mse_loss / softmax_kl_loss, which softmax again
+            float qs[C], qt[C], lse_qs, m_qs, lse_qt, m_qt;
+            softmax_c<C, FAST>(ps, qs, lse_qs, m_qs);
+            softmax_c<C, FAST>(pt, qt, lse_qt, m_qt);
+            if (cons_kind != 1) {
+                float d2 = 0.f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) { const float d = qs[c] - qt[c]; d2 += d * d; }
+                acc[SC_MSE] += d2;
+            }
+            if (cons_kind != 0) {
+                float kl = 0.f;     // log q = p - m - lse on both sides: no further log
+#pragma unroll
+                for (int c = 0; c < C; ++c) kl += qt[c] * ((pt[c] - m_qt - lse_qt) - (ps[c] - m_qs - lse_qs));
+                acc[SC_KL] += kl;
+            }
+        }
+        const float hs = entropy_c<C, FAST>(ps), ht = entropy_c<C, FAST>(pt);
+        const float w = fexp<FAST>(beta * hs) + fexp<FAST>(beta * ht);
+        float d2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) { const float e = ps[c] - pt[c]; d2 += e * e; }
+        acc[SC_UW] += fdiv<FAST>(d2, w);
+        acc[SC_UH] += hs + ht;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const float v = wave_sum(acc[k]);
+        if (lane == 0) red[wv][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        const double v = (double)red[0][threadIdx.x] + (double)red[1][threadIdx.x] + (double)red[2][threadIdx.x] + (double)red[3][threadIdx.x];
+        atomicAdd(&sums[threadIdx.x], v);
+    }
+}
+
+template <int C, bool FAST>
+__global__ __launch_bounds__(256) void seg_lossesc_bwd_kernel(const float* __restrict__ SL, const float* __restrict__ TL,
+                                                              const void* __restrict__ labels, int label_bytes, int B, int LB,
+                                                              long long V, float beta, const double* __restrict__ sums,
+                                                              const float* __restrict__ coef, int cons_kind, float* __restrict__ G) {
+    const float c_ce = coef[0], c_dfg = coef[1], c_dmc = coef[2] * (1.f / C), c_cons = coef[3], c_uncl = coef[4];
+    const float smooth = 1e-5f;
+    // per class: d dice_c / d p = kt[c] * t + kp[c] * p
+    float kt[C], kp[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float I = (float)sums[SC_DICE + 3 * c], D = (float)sums[SC_DICE + 3 * c + 1] + (float)sums[SC_DICE + 3 * c + 2] + smooth;
+        const float w = (c == 1 ? c_dfg : 0.f) + c_dmc, inv_Dsq = 1.f / (D * D);
+        kt[c] = -w * 2.f * D * inv_Dsq;
+        kp[c] = w * (2.f * I + smooth) * 2.f * inv_Dsq;
+    }
+    const float k_ce = LB > 0 ? c_ce / ((float)LB * (float)V) : 0.f;
+    const float inv_cons = B > LB ? 1.f / ((float)(B - LB) * (float)V * (float)C) : 0.f;
+    const float k_uncl = c_uncl / ((float)B * (float)V);
+    const long long total = (long long)B * V, lab_end = (long long)LB * V;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        float ls[C], lt[C], ps[C], pt[C];
+        load_row<C>(SL, i, ls);
+        load_row<C>(TL, i, lt);
+        float lse_s, m_s, lse_t, m_t;
+        softmax_c<C, FAST>(ls, ps, lse_s, m_s);
+        softmax_c<C, FAST>(lt, pt, lse_t, m_t);
+        float gp[C];   // d loss / d student probabilities
+        float gl[C];   // direct d loss / d logits (cross entropy)
+        if (i < lab_end) {
+            const int y = load_label(labels, label_bytes, i);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float tc = y == c ? 1.f : 0.f;
+                gl[c] = k_ce * (ps[c] - tc);
+                gp[c] = kt[c] * tc + kp[c] * ps[c];
+            }
+        } else {
+            float qs[C], qt[C], lse_q, m_q;
+            softmax_c<C, FAST>(ps, qs, lse_q, m_q);
+            softmax_c<C, FAST>(pt, qt, lse_q, m_q);
+            // gradient w.r.t. the inner softmax INPUT (= student probabilities)
+            if (cons_kind == 0) {
+                float a[C], dot = 0.f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) { a[c] = 2.f * (qs[c] - qt[c]) * inv_cons; dot += qs[c] * a[c]; }
+#pragma unroll
+                for (int c = 0; c < C; ++c) { gl[c] = 0.f; gp[c] = c_cons * qs[c] * (a[c] - dot); }
+            } else {
+#pragma unroll
+                for (int c = 0; c < C; ++c) { gl[c] = 0.f; gp[c] = c_cons * (qs[c] - qt[c]) * inv_cons; }
+            }
+        }
+        {
+            const float eps = 1e-6f;
+            float lps[C], hs = 0.f, d2 = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                lps[c] = flog<FAST>(ps[c] + eps);
+                hs -= ps[c] * lps[c];
+                const float e = ps[c] - pt[c];
+                d2 += e * e;
+            }
+            const float ht = entropy_c<C, FAST>(pt);
+            const float ehs = fexp<FAST>(beta * hs), w = ehs + fexp<FAST>(beta * ht);
+            const float rw = fdiv<FAST>(1.f, w);
+            const float k = beta - d2 * beta * ehs * rw * rw;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float dh = -(lps[c] + fdiv<FAST>(ps[c], ps[c] + eps));
+                gp[c] += k_uncl * (2.f * (ps[c] - pt[c]) * rw + dh * k);
+            }
+        }
+        float dot = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) dot += ps[c] * gp[c];
+#pragma unroll
+        for (int c = 0; c < C; ++c) gl[c] += ps[c] * (gp[c] - dot);
+        store_row<C>(G, i, gl);
+    }
+}
+
+struct VoxelValsC { float ce, dice_fg, dice_mc, mse, kl, uncl; };
+__device__ __forceinline__ VoxelValsC voxel_vals_c(const double* __restrict__ sums, int B, int LB, long long V, int C, float beta) {
+    const double s = 1e-5;
+    const double nl = (double)LB * (double)V, nc = (double)(B - LB) * (double)V * (double)C, na = (double)B * (double)V;
+    double dsum = 0.0, d1 = 0.0;
+    for (int c = 0; c < C; ++c) {
+        const double* q = sums + SC_DICE + 3 * c;
+        const double d = 1.0 - (2.0 * q[0] + s) / (q[1] + q[2] + s);
+        dsum += d;
+        if (c == 1) d1 = d;
+    }
+    VoxelValsC v;
+    v.ce = LB > 0 ? (float)(sums[SC_CE] / nl) : 0.f;
+    v.dice_fg = (float)d1;
+    v.dice_mc = (float)(dsum / (double)C);
+    v.mse = B > LB ? (float)(sums[SC_MSE] / nc) : 0.f;
+    v.kl = B > LB ? (float)(sums[SC_KL] / nc) : 0.f;
+    v.uncl = (float)(sums[SC_UW] / na + (double)beta * sums[SC_UH] / na);
+    return v;
+}
+
+// vals as seg_losses_finalize_kernel's
+__global__ void seg_lossesc_finalize_kernel(const double* __restrict__ sums, int B, int LB, long long V, int C, float beta,
+                                            float* __restrict__ vals) {
+    const VoxelValsC v = voxel_vals_c(sums, B, LB, V, C, beta);
+    vals[0] = v.ce; vals[1] = v.dice_fg; vals[2] = v.dice_mc; vals[3] = v.mse; vals[4] = v.kl; vals[5] = v.uncl;
+}
+
+// step_losses_kernel for C classes
+__global__ void step_lossesc_kernel(const double* __restrict__ sums, const double* __restrict__ fo, int B, int LB, long long V, int C,
+                                    float beta, double fecl_rows, float lambda_cross, int has_teacher, float l_w, float cons_w,
+                                    float u_w, int dice_kind, int cons_kind, float* __restrict__ out, int* __restrict__ nonfinite) {
+    const VoxelValsC v = voxel_vals_c(sums, B, LB, V, C, beta);
+    const float ce = v.ce, dice = dice_kind ? v.dice_mc : v.dice_fg, cons = cons_kind ? v.kl : v.mse, un = v.uncl;
+    float fe = 0.f;
+    if (fo) {
+        double l = fo[0] / fecl_rows;
+        if (has_teacher) l += (double)lambda_cross * fo[1] / (fo[2] + 1e-18);
+        fe = (float)l;
+    }
+    const float total = l_w * (ce + dice) + cons_w * cons + u_w * (fe + un);
+    out[0] = total; out[1] = ce; out[2] = dice; out[3] = cons; out[4] = fe; out[5] = un;
+    if (nonfinite) nonfinite[0] = isfinite(total) ? 0 : 1;
+}
+
+// =================================================================================================
 // row L2 normalisation: one wave per row
 // =================================================================================================
 template <typename T>
@@ -1245,6 +1509,79 @@ extern "C" int dycon_step_losses(const double* sums, const double* fecl_out, int
     DYCON_REQUIRE(sums && out && B > 0 && LB >= 0 && LB <= B && V > 0 && (!fecl_out || fecl_rows > 0), "step_losses: bad arguments");
     step_losses_kernel<<<1, 1, 0, stream>>>(sums, fecl_out, B, LB, V, beta, fecl_rows, lambda_cross, has_teacher, l_weight, cons_weight,
                                             u_weight, dice_kind, cons_kind, out, nonfinite);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+// ---- C classes
+#define DYCON_CLASSES(classes, ...)                                      \
+    switch (classes) {                                                   \
+        case 2: { constexpr int NCLS = 2; __VA_ARGS__ } break;           \
+        case 3: { constexpr int NCLS = 3; __VA_ARGS__ } break;           \
+        case 4: { constexpr int NCLS = 4; __VA_ARGS__ } break;           \
+        case 5: { constexpr int NCLS = 5; __VA_ARGS__ } break;           \
+        case 6: { constexpr int NCLS = 6; __VA_ARGS__ } break;           \
+        case 7: { constexpr int NCLS = 7; __VA_ARGS__ } break;           \
+        default: { constexpr int NCLS = 8; __VA_ARGS__ } break;          \
+    }
+
+extern "C" int dycon_seg_lossesc_nsums(int classes) { return classes >= 2 && classes <= 8 ? nsums_c(classes) : 0; }
+
+extern "C" int dycon_seg_lossesc_fwd(const float* s_logits, const float* t_logits, const void* labels, int label_bytes, int B,
+                                     int LB, long long V, int classes, float beta, int cons_kind, double* sums, int fast,
+                                     dycon_stream_t stream) {
+    DYCON_REQUIRE(s_logits && t_logits && sums && B > 0 && LB >= 0 && LB <= B && V > 0, "seg_lossesc_fwd: bad arguments");
+    DYCON_REQUIRE(classes >= 2 && classes <= 8, "seg_lossesc_fwd: classes must be in 2..8");
+    DYCON_REQUIRE(cons_kind >= 0 && cons_kind <= 2, "seg_lossesc_fwd: cons_kind must be 0 (mse), 1 (kl) or 2 (both)");
+    DYCON_REQUIRE(LB == 0 || labels, "seg_lossesc_fwd: labels missing");
+    DYCON_REQUIRE(label_bytes == 1 || label_bytes == 8, "seg_lossesc_fwd: labels must be uint8 or int64");
+    if (hipMemsetAsync(sums, 0, nsums_c(classes) * sizeof(double), stream) != hipSuccess) { dycon_set_error("seg_lossesc_fwd: memset failed"); return DYCON_ERR_LAUNCH; }
+    const int grid = lgrid((long long)B * V);      // as the 2-class pass: bound by the exp / log sequences
+    DYCON_CLASSES(classes, {
+        if (fast)
+            seg_lossesc_fwd_kernel<NCLS, true><<<grid, 256, 0, stream>>>(s_logits, t_logits, labels, label_bytes, B, LB, V, beta, cons_kind, sums);
+        else
+            seg_lossesc_fwd_kernel<NCLS, false><<<grid, 256, 0, stream>>>(s_logits, t_logits, labels, label_bytes, B, LB, V, beta, cons_kind, sums);
+    });
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_seg_lossesc_bwd(const float* s_logits, const float* t_logits, const void* labels, int label_bytes, int B,
+                                     int LB, long long V, int classes, float beta, const double* sums, const float* coef,
+                                     int cons_kind, float* g_logits, int fast, dycon_stream_t stream) {
+    DYCON_REQUIRE(s_logits && t_logits && sums && coef && g_logits && B > 0 && LB >= 0 && LB <= B && V > 0, "seg_lossesc_bwd: bad arguments");
+    DYCON_REQUIRE(classes >= 2 && classes <= 8, "seg_lossesc_bwd: classes must be in 2..8");
+    DYCON_REQUIRE(cons_kind == 0 || cons_kind == 1, "seg_lossesc_bwd: cons_kind must be 0 (mse) or 1 (kl)");
+    DYCON_REQUIRE(LB == 0 || labels, "seg_lossesc_bwd: labels missing");
+    DYCON_REQUIRE(label_bytes == 1 || label_bytes == 8, "seg_lossesc_bwd: labels must be uint8 or int64");
+    const int grid = lgrid((long long)B * V);
+    DYCON_CLASSES(classes, {
+        if (fast)
+            seg_lossesc_bwd_kernel<NCLS, true><<<grid, 256, 0, stream>>>(s_logits, t_logits, labels, label_bytes, B, LB, V, beta, sums, coef, cons_kind, g_logits);
+        else
+            seg_lossesc_bwd_kernel<NCLS, false><<<grid, 256, 0, stream>>>(s_logits, t_logits, labels, label_bytes, B, LB, V, beta, sums, coef, cons_kind, g_logits);
+    });
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_seg_lossesc_finalize(const double* sums, int B, int LB, long long V, int classes, float beta, float* vals,
+                                          dycon_stream_t stream) {
+    DYCON_REQUIRE(sums && vals && B > 0 && LB >= 0 && LB <= B && V > 0, "seg_lossesc_finalize: bad arguments");
+    DYCON_REQUIRE(classes >= 2 && classes <= 8, "seg_lossesc_finalize: classes must be in 2..8");
+    seg_lossesc_finalize_kernel<<<1, 1, 0, stream>>>(sums, B, LB, V, classes, beta, vals);
+    DYCON_LAUNCH_CHECK();
+    return DYCON_OK;
+}
+
+extern "C" int dycon_step_lossesc(const double* sums, const double* fecl_out, int B, int LB, long long V, int classes, float beta,
+                                  double fecl_rows, float lambda_cross, int has_teacher, float l_weight, float cons_weight,
+                                  float u_weight, int dice_kind, int cons_kind, float* out, int* nonfinite, dycon_stream_t stream) {
+    DYCON_REQUIRE(sums && out && B > 0 && LB >= 0 && LB <= B && V > 0 && (!fecl_out || fecl_rows > 0), "step_lossesc: bad arguments");
+    DYCON_REQUIRE(classes >= 2 && classes <= 8, "step_lossesc: classes must be in 2..8");
+    step_lossesc_kernel<<<1, 1, 0, stream>>>(sums, fecl_out, B, LB, V, classes, beta, fecl_rows, lambda_cross, has_teacher, l_weight,
+                                             cons_weight, u_weight, dice_kind, cons_kind, out, nonfinite);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }

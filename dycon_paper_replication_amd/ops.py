@@ -716,6 +716,51 @@ def step_losses(sums, fecl_out, B, LB, V, beta, fecl_rows, lambda_cross, has_tea
     return out
 
 
+def seg_lossesc_nsums(classes):
+    """doubles of the C-class accumulator: ce, mse, kl, uncl_w, uncl_h, then I_c, Z_c, Y_c per class"""
+    n = _lib.query("dycon_seg_lossesc_nsums", int(classes))
+    if n <= 0:
+        raise ValueError(f"the C-class voxel losses take 2..8 classes, got {classes}")
+    return n
+
+
+def seg_lossesc_fwd(s_logits, t_logits, labels, LB, beta, cons_kind=2, fast=False, out=None):
+    """s/t_logits: (B, D, H, W, C) fp32, C in 2..8 (the last axis); returns sums (5 + 3C doubles on device; `out`: the caller's
+    buffer).  cons_kind 0: mse sum only, 1: kl only, 2: both.  fast: hardware exp/log sequences (bf16 step)."""
+    B, C = s_logits.shape[0], s_logits.shape[-1]
+    V = s_logits.numel() // (C * B)
+    n = seg_lossesc_nsums(C)
+    sums = out if out is not None else torch.empty(n, dtype=torch.float64, device=s_logits.device)
+    assert sums.numel() >= n and t_logits.shape == s_logits.shape
+    call("dycon_seg_lossesc_fwd", _p(s_logits), _p(t_logits), _p(labels), _label_bytes(labels), B, LB, V, C, float(beta), int(cons_kind),
+         _p(sums), int(fast), _s())
+    return sums
+
+
+def seg_lossesc_bwd(s_logits, t_logits, labels, LB, beta, sums, coef, cons_kind=0, fast=False):
+    B, C = s_logits.shape[0], s_logits.shape[-1]
+    V = s_logits.numel() // (C * B)
+    g = torch.empty_like(s_logits)
+    call("dycon_seg_lossesc_bwd", _p(s_logits), _p(t_logits), _p(labels), _label_bytes(labels), B, LB, V, C, float(beta), _p(sums),
+         _p(coef), cons_kind, _p(g), int(fast), _s())
+    return g
+
+
+def seg_lossesc_finalize(sums, B, LB, V, classes, beta):
+    vals = torch.empty(8, dtype=torch.float32, device=sums.device)
+    call("dycon_seg_lossesc_finalize", _p(sums), B, LB, V, int(classes), float(beta), _p(vals), _s())
+    return vals
+
+
+def step_lossesc(sums, fecl_out, B, LB, V, classes, beta, fecl_rows, lambda_cross, has_teacher, l_w, cons_w, u_w, dice_kind, cons_kind,
+                 nonfinite=None):
+    """step_losses for C classes, from the 5 + 3C accumulators of seg_lossesc_fwd"""
+    out = torch.empty(8, dtype=torch.float32, device=sums.device)
+    call("dycon_step_lossesc", _p(sums), _p(fecl_out), B, LB, V, int(classes), float(beta), float(fecl_rows), float(lambda_cross),
+         int(bool(has_teacher)), float(l_w), float(cons_w), float(u_w), dice_kind, cons_kind, _p(out), _p(nonfinite), _s())
+    return out
+
+
 def step_loss(vals, fecl, l_w, cons_w, u_w, dice_kind, cons_kind, nonfinite=None):
     out = torch.empty(8, dtype=torch.float32, device=vals.device)
     call("dycon_step_loss", _p(vals), _p(fecl), float(l_w), float(cons_w), float(u_w), dice_kind, cons_kind, _p(out),

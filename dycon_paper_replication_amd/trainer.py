@@ -11,7 +11,7 @@ out right after the loss and waited for at the end of the step (the backward is 
 
 Multi-GPU (one process per GPU, ``torch.distributed`` backend "nccl" == RCCL over xGMI): the batch
 is sharded [labelled | unlabelled] per rank; one all-reduce of the flat gradient arena after the
-backward, plus two tiny all-reduces (16 + 4 doubles) that keep the reference's batch-global
+backward, plus two tiny all-reduces (16 + 4 doubles; (5 + 3C) + 4 for C != 2 classes) that keep the reference's batch-global
 semantics of the Dice ratio and of the FeCL cross-branch ratio.
 """
 from __future__ import annotations
@@ -37,6 +37,7 @@ class TrainConfig:
     model: str = "vnet"                 # "vnet" | "unet_3D"
     use_aspp: bool = False              # unet_3D: ASPP3D before the projection head (net_factory_3d(use_aspp=True))
     normalization: str = "groupnorm"    # V-Net only
+    num_classes: int = 2                # --num_classes, 2..8: width of the segmentation heads (class 1 of the softmax is scored)
     max_iterations: int = 20000
     batch_size: int = 8                 # per process
     labeled_bs: int = 4                 # per process
@@ -78,6 +79,12 @@ class TrainConfig:
                                         # re-issue it with patched scalars (the step is host-enqueue-bound: see DyconTrainer.step);
                                         # single-process and data-parallel runs alike
 
+    def __post_init__(self):
+        if not isinstance(self.num_classes, int) or not 2 <= self.num_classes <= 8:
+            raise ValueError(f"num_classes must be an integer in 2..8, got {self.num_classes!r}")
+        if self.use_gambling and self.num_classes != 2:
+            raise ValueError(f"use_gambling=1 needs num_classes=2 (the gambling-uncertainty kernels are 2-class), got {self.num_classes}")
+
 
 def bucket_cuts(head_offsets, n_sgd, nb=4, tail_frac=0.06):
     """Arena offsets at which the flat gradient buffer [0, n_sgd) is cut into at most `nb` all-reduce buckets; every cut is one of
@@ -107,7 +114,7 @@ class DyconTrainer:
         # the data-parallel exchange (bucketed gradient all-reduce, 16 + 4-double loss exchange); ddp_force runs it with ONE rank too,
         # where every collective is the identity (tests: the RCCL calls inside the recorded step, on the single GPU of a test box)
         self.ddp = self.world > 1 or (cfg.ddp_force and process_group is not None)
-        spec = param_spec(cfg.model, 1, 2, cfg.normalization, cfg.use_aspp)
+        spec = param_spec(cfg.model, 1, cfg.num_classes, cfg.normalization, cfg.use_aspp)
         # parameters the loss never reaches keep grad=None in the reference and are skipped by
         # clip_grad_norm_/SGD (weight decay included): put them behind the SGD range of the arena
         nograd = [k for k in spec if k.startswith("final.")]
@@ -135,9 +142,9 @@ class DyconTrainer:
         self.g = OrderedDict((k, view(self.flat_g, k)) for k in spec)
 
         # nn.Module shells (state_dict / eval-mode inference); their parameters alias the arenas
-        self.model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
+        self.model = net_factory_3d(cfg.model, 1, cfg.num_classes, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
                                     normalization=cfg.normalization)
-        self.ema_model = net_factory_3d(cfg.model, 1, 2, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
+        self.ema_model = net_factory_3d(cfg.model, 1, cfg.num_classes, cfg.feature_scaler, use_aspp=cfg.use_aspp, dtype=cfg.dtype,
                                         normalization=cfg.normalization)
         g0 = torch.Generator().manual_seed(cfg.seed)
         for mod, init, arena in ((self.model, student_init, self.p), (self.ema_model, teacher_init, self.t)):
@@ -165,7 +172,10 @@ class DyconTrainer:
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=self.device)
         self.flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.coef = torch.zeros(8, dtype=torch.float32, device=self.device)
-        self.acc20 = torch.zeros(20, dtype=torch.float64, device=self.device)      # [0:16] voxel-loss sums, [16:20] FeCL accumulators
+        # the step's loss accumulators in ONE buffer (one all-reduce in a data-parallel run): the voxel-loss sums, then FeCL's four.
+        # Two classes: the 2-class pass and its 16 + 4 layout; otherwise the C-class pass's (5 + 3C) + 4
+        self.n_sums = 16 if cfg.num_classes == 2 else ops.seg_lossesc_nsums(cfg.num_classes)
+        self.acc20 = torch.zeros(self.n_sums + 4, dtype=torch.float64, device=self.device)
         self.skipped_steps = 0
         # the NaN/Inf flag is final once step_loss has run: it is copied to pinned host memory right there and read at the end
         # of the step, when the copy has long completed -- the host never waits for the backward, the GPU never runs dry
@@ -332,7 +342,8 @@ class DyconTrainer:
         for name, (idx, stride) in self._PHILOX.items():
             for e in by.get(name, ()):
                 e[1][idx] = base[id(e)][idx] + (it - rp["it"]) * stride
-        for name, idx in (("dycon_seg_losses_fwd", 7), ("dycon_seg_losses_bwd", 7), ("dycon_step_losses", 5)):
+        for name, idx in (("dycon_seg_losses_fwd", 7), ("dycon_seg_losses_bwd", 7), ("dycon_step_losses", 5),
+                          ("dycon_seg_lossesc_fwd", 8), ("dycon_seg_lossesc_bwd", 8), ("dycon_step_lossesc", 6)):
             for e in by.get(name, ()):
                 e[1][idx] = float(beta)
         for name in ("dycon_fecl_fwd", "dycon_fecl_bwd"):
@@ -342,6 +353,8 @@ class DyconTrainer:
             e[1][9] = thr
         for e in by.get("dycon_step_losses", ()):
             e[1][10] = float(cw)
+        for e in by.get("dycon_step_lossesc", ()):
+            e[1][11] = float(cw)
         for e in by.get("dycon_set_scalars", ()):           # coef = (l_w, l_w*(1-dk)*gw, l_w*dk*gw, cw, u_w, u_w): only cw moves
             e[1][5] = float(cw)
         for e in by.get("dycon_sgd_ema", ()):
@@ -437,8 +450,13 @@ class DyconTrainer:
         # ---- losses (:308-357)
         world = self.world
         # the step's 16 + 4 loss accumulators live in ONE buffer: a data-parallel run exchanges them with one all-reduce
-        sums, fo = self.acc20[:16], self.acc20[16:]
-        ops.seg_losses_fwd(s_logits, t_logits, label, LB, beta, fast=self._fast_math, out=sums)
+        NC = c.num_classes
+        cons_kind = 0 if c.consistency_type == "mse" else 1
+        sums, fo = self.acc20[:self.n_sums], self.acc20[self.n_sums:]
+        if NC == 2:
+            ops.seg_losses_fwd(s_logits, t_logits, label, LB, beta, fast=self._fast_math, out=sums)
+        else:
+            ops.seg_lossesc_fwd(s_logits, t_logits, label, LB, beta, cons_kind, fast=self._fast_math, out=sums)
         k = (D // s_feat.shape[1], H // s_feat.shape[2], W // s_feat.shape[3])     # patch size per axis of the feature grid
         gmb = bool(c.use_gambling)
         if gmb:   # u = interpolate(entropy(gambling_softmax(stud_logits)), 1/k) (Pancreas :242-246), on main beside the feature branch
@@ -478,16 +496,20 @@ class DyconTrainer:
             # global count (dycon_losses.py:229): exchange the 16 + 4 accumulators (one collective), then finalise on every rank
             acc20 = self.acc20
             ops.rec(lambda: torch.distributed.all_reduce(acc20, group=self.pg))
-        cons_kind = 0 if c.consistency_type == "mse" else 1
         # the scalar end of the loss forward (:355-362) in one launch: voxel-loss ratios, FeCL finalize, weighted total, NaN/Inf flag
-        out = ops.step_losses(sums, fo, B * gw, LB * gw, V, beta, B * gw * s_emb.shape[1], 1.0, teacher_emb is not None,
-                              c.l_weight, cw, c.u_weight, dice_kind, cons_kind, self.flag)
+        if NC == 2:
+            out = ops.step_losses(sums, fo, B * gw, LB * gw, V, beta, B * gw * s_emb.shape[1], 1.0, teacher_emb is not None,
+                                  c.l_weight, cw, c.u_weight, dice_kind, cons_kind, self.flag)
+        else:
+            out = ops.step_lossesc(sums, fo, B * gw, LB * gw, V, NC, beta, B * gw * s_emb.shape[1], 1.0, teacher_emb is not None,
+                                   c.l_weight, cw, c.u_weight, dice_kind, cons_kind, self.flag)
         if c.strict_nan_check:
             ops.rec(lambda: (self.flag_host.copy_(self.flag, non_blocking=True), self.flag_evt.record(main)))
 
         # ---- backward (:364-365); coef was written at the head of the step
         self._mark("loss_end")
-        g_logits = ops.seg_losses_bwd(s_logits, t_logits, label, LB, beta, sums, self.coef, cons_kind, fast=self._fast_math)
+        seg_bwd = ops.seg_losses_bwd if NC == 2 else ops.seg_lossesc_bwd
+        g_logits = seg_bwd(s_logits, t_logits, label, LB, beta, sums, self.coef, cons_kind, fast=self._fast_math)
         if gmb:    # FeCL's gradient into the student's logits through u (the 8 voxels of each patch), before the backward reads g_logits
             ops.gambling_uncertainty_bwd(s_logits, k, gu, g_logits, fast=self._fast_math)
         if self.feat is not None:

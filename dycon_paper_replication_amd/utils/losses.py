@@ -12,7 +12,7 @@ Two families:
   ``FeCLoss(device, temperature)``, with the reference's quirks kept (plain sums in ``dice_loss1``, gradient to BOTH sides
   of ``softmax_dice_loss``, the last-dimension softmax of ``compute_kl_loss``, the detached ``pt`` of ``FocalLoss``);
 * the fast forms the fused trainer uses: ONE pass over the logits for every voxel loss
-  (``fused_voxel_losses`` and the ``*_from_logits`` / ``*_mean`` wrappers; the 2-class softmax is part of the kernel).
+  (``fused_voxel_losses`` and the ``*_from_logits`` / ``*_mean`` wrappers, 2..8 classes; the softmax is part of the kernel).
 """
 from __future__ import annotations
 
@@ -62,10 +62,54 @@ class _VoxelLossFunction(torch.autograd.Function):
         return out.permute(0, 4, 1, 2, 3), None, None, None, None
 
 
+class _VoxelLossClassesFunction(torch.autograd.Function):
+    """_VoxelLossFunction for 3..8 classes: the C-class pass (dycon_seg_lossesc_*), both consistency kinds accumulated."""
+
+    @staticmethod
+    def forward(ctx, s_logits, t_logits, labels, labeled_bs, beta):
+        s, t = _ndhwc_logits_c(s_logits), _ndhwc_logits_c(t_logits)
+        B, C = s.shape[0], s.shape[-1]
+        V = s.numel() // (C * B)
+        lab = labels.contiguous()
+        sums = ops.seg_lossesc_fwd(s, t, lab, labeled_bs, beta, cons_kind=2)
+        vals = ops.seg_lossesc_finalize(sums, B, labeled_bs, V, C, beta)
+        ctx.save_for_backward(s, t, sums, lab)
+        ctx.meta = (labeled_bs, beta)
+        return vals[:6]
+
+    @staticmethod
+    def backward(ctx, g):
+        s, t, sums, lab = ctx.saved_tensors
+        LB, beta = ctx.meta
+        g = g.float()
+        out = None
+        for kind, cons_g in ((0, g[CONS_MSE:CONS_MSE + 1]), (1, g[CONS_KL:CONS_KL + 1])):
+            coef = torch.zeros(5, dtype=torch.float32, device=s.device)
+            if kind == 0:
+                coef[0:3] = g[0:3]
+                coef[4:5] = g[UNCL:UNCL + 1]
+            coef[3:4] = cons_g
+            part = ops.seg_lossesc_bwd(s, t, lab, LB, beta, sums, coef, kind)
+            out = part if out is None else ops.add(out, part)
+        return out.permute(0, 4, 1, 2, 3), None, None, None, None
+
+
+def _ndhwc_logits_c(x):
+    """(B,C,D,H,W) any strides -> contiguous fp32 (B,D,H,W,C), C in 2..8"""
+    if x.dim() != 5 or not 2 <= x.shape[1] <= 8:
+        raise ValueError(f"expected logits (B,C,D,H,W) with C in 2..8, got {tuple(x.shape)}")
+    return x.permute(0, 2, 3, 4, 1).contiguous().float()
+
+
 def fused_voxel_losses(s_logits, t_logits, labels, labeled_bs, beta=1.0):
-    """One pass over student/teacher logits (B,2,D,H,W) and labels (B,D,H,W): returns the 6 scalars
-    (ce, dice_fg, dice_multiclass, cons_mse, cons_kl, uncl) as a differentiable tensor (train_DyCON_BraTS19.py:308-352)."""
-    return _VoxelLossFunction.apply(s_logits, t_logits.detach(), labels, int(labeled_bs), float(beta))
+    """One pass over student/teacher logits (B,C,D,H,W), C in 2..8, and labels (B,D,H,W): returns the 6 scalars
+    (ce, dice_fg, dice_multiclass, cons_mse, cons_kl, uncl) as a differentiable tensor (train_DyCON_BraTS19.py:308-352).
+    Two classes run the 2-class kernels, any other count the C-class ones; dice_fg scores class 1 either way."""
+    if s_logits.dim() != 5 or not 2 <= s_logits.shape[1] <= 8 or s_logits.shape != t_logits.shape:
+        raise ValueError(f"fused_voxel_losses: expected two (B,C,D,H,W) logit tensors with C in 2..8, got {tuple(s_logits.shape)} "
+                         f"and {tuple(t_logits.shape)}")
+    fn = _VoxelLossFunction if s_logits.shape[1] == 2 else _VoxelLossClassesFunction
+    return fn.apply(s_logits, t_logits.detach(), labels, int(labeled_bs), float(beta))
 
 
 def dice_loss_from_logits(logits, target):
@@ -75,7 +119,7 @@ def dice_loss_from_logits(logits, target):
 
 
 def cross_entropy_from_logits(logits, target):
-    """F.cross_entropy(logits, target) for 2 classes (train_DyCON_BraTS19.py:313)."""
+    """F.cross_entropy(logits, target) for 2..8 classes (train_DyCON_BraTS19.py:313)."""
     return fused_voxel_losses(logits, logits, target, logits.shape[0])[CE]
 
 

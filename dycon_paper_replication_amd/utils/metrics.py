@@ -33,11 +33,23 @@ def _counts(logits_ndhwc2, labels):
     return out.double()
 
 
+def _two_class_ndhwc(logits):
+    """(B, 2, D, H, W) or (B, D, H, W, 2) -> the (B, D, H, W, 2) view; any other class width is refused here, before a kernel is sized
+    with it (the train-time metrics are 2-class)."""
+    if logits.dim() != 5:
+        raise ValueError(f"expected 5-D logits (B, 2, D, H, W) or (B, D, H, W, 2), got {tuple(logits.shape)}")
+    lg = logits if logits.shape[-1] == 2 and logits.shape[1] != 2 else logits.permute(0, 2, 3, 4, 1)
+    if lg.shape[-1] != 2:
+        raise ValueError(f"the train-time metrics take 2-class logits, got a class axis of width {lg.shape[-1]} "
+                         f"(shape {tuple(logits.shape)})")
+    return lg
+
+
 def batch_dice_from_logits(logits, labels):
     """logits (B, 2, D, H, W) as the HIP nets return them (channels-last-3D view) or (B, D, H, W, 2); labels (B, D, H, W).
     Per-sample Dice of (softmax(logits)[:, 1] > 0.5) against labels, = metrics.compute_dice(outputs_bin, label) of the reference
     (train_DyCON_BraTS19.py:387-389), as a device tensor (no sync)."""
-    lg = logits if logits.shape[-1] == 2 and logits.dim() == 5 and logits.shape[1] != 2 else logits.permute(0, 2, 3, 4, 1)
+    lg = _two_class_ndhwc(logits)
     c = _counts(lg.contiguous().float(), labels)
     return 2.0 * c[:, 2] / (c[:, 0] + c[:, 1] + 1e-8)
 
@@ -115,10 +127,10 @@ class AsyncTrainMetrics:
             self._hd = (it, float(np.mean(compute_hd95(pred.numpy(), lab.numpy(), max_dist))))
 
     def update(self, iter_num, logits, labels):
+        lg = _two_class_ndhwc(logits)
         self._iter = iter_num
         self._dice = batch_dice_from_logits(logits, labels)
         if self.every and iter_num % self.every == 0 and not self._q.full():
-            lg = logits if logits.shape[-1] == 2 and logits.shape[1] != 2 else logits.permute(0, 2, 3, 4, 1)
             pred = (lg[..., 1] > lg[..., 0]).to(torch.uint8)
             ph = torch.empty(pred.shape, dtype=torch.uint8).pin_memory()
             lh = torch.empty(labels.shape, dtype=torch.uint8).pin_memory()

@@ -370,6 +370,40 @@ int dycon_step_losses(const double* sums, const double* fecl_out, int B, int LB,
                       float u_weight, int dice_kind, int cons_kind, float* out, int* nonfinite,
                       dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- voxel losses (C classes, 2 <= classes <= 8)
+ * The same pass for logits (B, V, classes) fp32 rows (channels-last, as the nets' heads write them); the 2-class entry points
+ * above keep their code and bits.  sums holds dycon_seg_lossesc_nsums(classes) = 5 + 3 * classes doubles (zeroed by _fwd):
+ *   0 ce_sum   1 mse_sum   2 kl_sum   3 uncl_w   4 uncl_h   5 + 3c: I_c  Z_c  Y_c   (c = 0 .. classes - 1)
+ * with I_c = sum p_c [y == c], Z_c = sum p_c^2, Y_c = sum [y == c] over the labelled samples [0, LB), p = softmax(s_logits).
+ *   ce          nn.CrossEntropyLoss()(logits[:LB], label[:LB].long())                      train_DyCON_BraTS19.py:313
+ *   dice "fg"   losses.dice_loss(softmax[:LB, 1], label[:LB] == 1), class 1 only           train_DyCON_BraTS19.py:314, utils/losses.py:8-16
+ *   dice "mc"   losses.DiceLoss(C)(softmax[:LB], label[:LB].unsqueeze(1)): mean over c of 1 - (2 I_c + s) / (Z_c + Y_c + s), s = 1e-5
+ *                                                                                          train_DyCON_ISLES22.py:247, utils/losses.py:156-192
+ *   mse / kl    softmax_mse_loss(p_s, p_t).mean() / softmax_kl_loss(p_s, p_t) on samples [LB, B): the reference passes PROBABILITIES,
+ *               which these softmax again; both means run over (B - LB) V classes elements    utils/losses.py:65-104
+ *   uncl        UnCLoss()(s_logits, t_logits, beta) on all B samples, log(p + 1e-6)         utils/dycon_losses.py:94-118
+ * A label >= classes is a caller error; the kernels select by comparison and never index with it (such a voxel adds its
+ * log-sum-exp to ce_sum and nothing to Y).
+ * _fwd cons_kind: 0 accumulates mse_sum only, 1 kl_sum only, 2 both (the pass is bound by its exp / log sequences).
+ * fast as dycon_seg_losses_fwd. */
+int dycon_seg_lossesc_nsums(int classes);   /* 5 + 3 * classes; 0 for classes outside 2..8 */
+int dycon_seg_lossesc_fwd(const float* s_logits, const float* t_logits, const void* labels, int label_bytes, int B, int LB,
+                          long long V, int classes, float beta, int cons_kind, double* sums, int fast, dycon_stream_t stream);
+/* g_logits = sum_k coef[k] * d(loss_k)/d(s_logits); coef (device, 5 floats) as dycon_seg_losses_bwd: ce, dice_fg, dice_multiclass,
+ * consistency (cons_kind 0: mse, 1: kl), uncl.  Needs the sums of the forward call (the Dice ratios; after a data-parallel
+ * exchange the global ones). */
+int dycon_seg_lossesc_bwd(const float* s_logits, const float* t_logits, const void* labels, int label_bytes, int B, int LB,
+                          long long V, int classes, float beta, const double* sums, const float* coef, int cons_kind,
+                          float* g_logits, int fast, dycon_stream_t stream);
+/* vals[6] as dycon_seg_losses_finalize: ce, dice(class 1), dice(mean over classes), cons mse, cons kl, uncl */
+int dycon_seg_lossesc_finalize(const double* sums, int B, int LB, long long V, int classes, float beta, float* vals,
+                               dycon_stream_t stream);
+/* dycon_step_losses from the C-class accumulators (train_DyCON_BraTS19.py:355-362, train_DyCON_ISLES22.py:302-308): out[6] and
+ * nonfinite as there; B, LB, fecl_rows are the GLOBAL counts after a data-parallel all-reduce of sums and fecl_out. */
+int dycon_step_lossesc(const double* sums, const double* fecl_out, int B, int LB, long long V, int classes, float beta,
+                       double fecl_rows, float lambda_cross, int has_teacher, float l_weight, float cons_weight,
+                       float u_weight, int dice_kind, int cons_kind, float* out, int* nonfinite, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- the reference's loss callables, reference semantics
  * The fused pass above takes LOGITS; the reference's own step body instead calls utils/losses.py on PROBABILITIES it computed
  * with torch (train_DyCON_BraTS19.py:308-314,352).  These entry points implement those callables literally, so that loop body
