@@ -136,6 +136,11 @@ SIGNATURES = {
     "dycon_sw_finalize": (I, [P, P, L, F, P, P, P]),
     "dycon_binary_overlap": (I, [P, P, I, L, P, P]),
     "dycon_batch_overlap": (I, [P, P, I, I, L, P, P]),
+    "dycon_sw_accumulate_all": (I, [P, I, I, I, I, I, P, P, P, I, I, I, P, P, P]),
+    "dycon_sw_finalize_argmax": (I, [P, P, I, L, P, P, P]),
+    "dycon_argmax_labels": (I, [P, I, L, P, P]),
+    "dycon_class_confusion": (I, [P, P, I, L, I, P, P]),
+    "dycon_batch_class_confusion": (I, [P, P, I, I, L, I, P, P]),
     "dycon_simhist_workspace": (Z, [I, I, I, I]),
     "dycon_simhist": (I, [P, P, I, I, I, I, F, I, P, P, P, P, Z, P]),
     "dycon_tap_gather": (I, [P, P, I, I, I, I, I, I, P, I, P]),

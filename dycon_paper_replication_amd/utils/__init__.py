@@ -6,3 +6,6 @@ from . import sliding_window, test_3d_patch  # noqa: F401
 # the class-count form (utils/sliding_window.py, which hands 2-class nets to the original) under that name: test_all_case, the
 # var_all_case_* / test_all_case_* wrappers and every caller of utils.test_3d_patch.test_single_case resolve it at call time.
 test_3d_patch.test_single_case = sliding_window.test_single_case
+
+# the all-class evaluator and the per-class metrics come beside it under names of their own and rebind nothing
+from . import eval_classes  # noqa: E402,F401

@@ -8,6 +8,10 @@ of the binary volumes plus two distance transforms per sample: more host time th
   * `compute_hd95` keeps the reference's semantics (max_dist for an empty mask) on scipy ("parity unpinned": medpy absent);
   * `AsyncTrainMetrics` takes it off the critical path: every `every`-th iteration the binary maps are copied to pinned memory
     asynchronously and a worker thread computes HD95 while the GPU trains on.
+
+Those names are 2-class and refuse another width.  For 2..8 classes, under names of their own: `class_dice_from_logits` (per sample
+and foreground class, from one confusion count over the logits, csrc/evalc.hip), `AsyncClassTrainMetrics`, the device path of
+`cal_dice`, and the reference's `dice` (utils/metrics.py:39-75), which its ISLES script validates with.
 """
 from __future__ import annotations
 
@@ -77,8 +81,95 @@ def compute_jaccard(output, label):
     return c[:, 2] / (c[:, 0] + c[:, 1] - c[:, 2] + 1e-8)
 
 
+def _check_classes(C):
+    if not 2 <= int(C) <= 8:
+        raise ValueError(f"the class-count metrics take 2..8 classes, got {C}")
+    return int(C)
+
+
+def _label_operand(t):
+    """ground-truth labels as the confusion kernels read them: uint8 or int64, contiguous"""
+    return (t if t.dtype in (torch.uint8, torch.int64) else t.to(torch.int64)).contiguous()
+
+
+def _class_confusion(pred, gt, C):
+    """CUDA label maps -> the (C*C + 1,) int64 counters of dycon_class_confusion: [p*C + g] and, last, the voxels whose prediction or
+    label lies outside [0, C).  No host sync."""
+    C = _check_classes(C)
+    if pred.numel() != gt.numel():
+        raise ValueError(f"prediction {tuple(pred.shape)} and label {tuple(gt.shape)} differ in size")
+    if pred.dtype != torch.uint8:       # the kernel reads uint8 predictions: keep an out-of-range value out of range
+        pred = torch.where((pred < 0) | (pred >= C), 255, pred).to(torch.uint8)
+    p, g = pred.contiguous(), _label_operand(gt.to(pred.device))
+    out = torch.zeros(C * C + 1, dtype=torch.int64, device=p.device)
+    _lib.call("dycon_class_confusion", p.data_ptr(), g.data_ptr(), g.element_size(), p.numel(), C, out.data_ptr(),
+              torch.cuda.current_stream().cuda_stream)
+    return out
+
+
+def _class_ndhwc(logits, labels):
+    """(B, C, D, H, W) (what the HIP nets return: a channels-last-3D view) or (B, D, H, W, C) -> the (B, D, H, W, C) view.  The labels'
+    (B, D, H, W) say which of the two it is."""
+    if logits.dim() != 5 or labels.dim() != 4:
+        raise ValueError(f"expected 5-D logits and (B, D, H, W) labels, got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    if logits.shape[:1] + logits.shape[2:] == labels.shape:
+        lg = logits.permute(0, 2, 3, 4, 1)
+    elif logits.shape[:-1] == labels.shape:
+        lg = logits
+    else:
+        raise ValueError(f"logits {tuple(logits.shape)} do not match labels {tuple(labels.shape)}")
+    _check_classes(lg.shape[-1])
+    return lg
+
+
+def class_dice_from_logits(logits, labels):
+    """logits (B, C, D, H, W) or (B, D, H, W, C), C in 2..8; labels (B, D, H, W) with values in [0, C).  Per sample and foreground
+    class 1..C-1 the Dice of argmax(logits) against labels, 2 I / (P + G + 1e-8) (cal_dice's arithmetic, utils/metrics.py:14-27), as a
+    (B, C-1) float64 device tensor: the counts come from the logits in one pass (dycon_batch_class_confusion), no host sync.  A voxel
+    whose label lies outside [0, C) is counted for no class."""
+    return _class_dice_ndhwc(_class_ndhwc(logits, labels).contiguous().float(), labels)
+
+
+def _class_dice_ndhwc(lg, labels):
+    B, C = lg.shape[0], lg.shape[-1]
+    lab = _label_operand(labels)
+    out = torch.zeros((B, C * C + 1), dtype=torch.int64, device=lg.device)
+    _lib.call("dycon_batch_class_confusion", lg.data_ptr(), lab.data_ptr(), lab.element_size(), B, lg.numel() // (B * C), C,
+              out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    conf = out[:, :C * C].reshape(B, C, C).double()                         # [b, pred, gt]
+    inter = torch.diagonal(conf, dim1=1, dim2=2)
+    return (2.0 * inter / (conf.sum(2) + conf.sum(1) + 1e-8))[:, 1:]
+
+
+def dice(input, target, ignore_index=None):
+    """The reference's `dice` (utils/metrics.py:39-75): (2 sum(i * t) + 1) / (sum(i) + sum(t) + 1) over all elements, both sides zeroed
+    where target == ignore_index.  numpy arrays (taken as float32, as the reference does) or tensors; computed on the device, returned
+    as a 0-dim device tensor."""
+    smooth = 1.0
+    if isinstance(input, np.ndarray):
+        input = torch.from_numpy(input.astype(np.float32))
+    if isinstance(target, np.ndarray):
+        target = torch.from_numpy(target.astype(np.float32))
+    dev = input.device if input.is_cuda else target.device if target.is_cuda else torch.device("cuda")
+    iflat, tflat = input.to(dev).reshape(-1), target.to(dev).reshape(-1)
+    if ignore_index is not None:
+        mask = tflat == ignore_index
+        iflat, tflat = iflat.masked_fill(mask, 0), tflat.masked_fill(mask, 0)
+    dt = torch.promote_types(iflat.dtype, tflat.dtype)
+    dt = dt if dt.is_floating_point else torch.float32
+    inter, total = (iflat.double() * tflat.double()).sum(), iflat.double().sum() + tflat.double().sum()
+    return ((2.0 * inter + smooth) / (total + smooth)).to(dt)
+
+
 def cal_dice(prediction, label, num=2):
-    """Multi-class Dice on label maps, classes 1..num-1 (utils/metrics.py:14-27); numpy in, numpy out."""
+    """Multi-class Dice on label maps, classes 1..num-1 (utils/metrics.py:14-27); numpy in, numpy out.  Two CUDA tensors are counted
+    on the device (dycon_class_confusion) and give the num - 1 values as a float64 device tensor, without a host sync."""
+    if torch.is_tensor(prediction) and torch.is_tensor(label) and prediction.is_cuda and label.is_cuda:
+        # a value outside [0, num) equals no i of the loop below on its own side only: fold it into class 0, which is not reported,
+        # so that the voxel still counts for the other side's class
+        fold = lambda t: torch.where((t < 0) | (t >= num), 0, t)  # noqa: E731
+        conf = _class_confusion(fold(prediction), fold(label), num)[:num * num].reshape(num, num).double()          # [pred, gt]
+        return (2.0 * torch.diagonal(conf) / (conf.sum(1) + conf.sum(0) + 1e-8))[1:]
     total = np.zeros(num - 1)
     for i in range(1, num):
         p, g = (np.asarray(prediction) == i), (np.asarray(label) == i)
@@ -145,3 +236,24 @@ class AsyncTrainMetrics:
 
     def close(self):
         self._q.put(None)
+
+
+class AsyncClassTrainMetrics(AsyncTrainMetrics):
+    """AsyncTrainMetrics for 2..8 classes: `class_dice_from_logits` every iteration ("dice": a (B, C-1) device tensor), and every
+    `every`-th iteration the HD95 of class 1 (argmax == 1 against label == 1) on the worker thread."""
+
+    def update(self, iter_num, logits, labels):
+        lg = _class_ndhwc(logits, labels).contiguous().float()
+        self._iter = iter_num
+        self._dice = _class_dice_ndhwc(lg, labels)
+        if self.every and iter_num % self.every == 0 and not self._q.full():
+            arg = torch.empty(labels.shape, dtype=torch.uint8, device=lg.device)
+            _lib.call("dycon_argmax_labels", lg.data_ptr(), lg.shape[-1], arg.numel(), arg.data_ptr(),
+                      torch.cuda.current_stream().cuda_stream)
+            ph = torch.empty(labels.shape, dtype=torch.uint8).pin_memory()
+            lh = torch.empty(labels.shape, dtype=torch.uint8).pin_memory()
+            ph.copy_(arg.eq(1).to(torch.uint8), non_blocking=True)
+            lh.copy_(labels.eq(1).to(torch.uint8), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._q.put((iter_num, ev, ph, lh, float(np.linalg.norm(labels.shape[1:]))))

@@ -585,6 +585,32 @@ int dycon_binary_overlap(const uint8_t* pred, const void* gt, int gt_bytes, long
 int dycon_batch_overlap(const float* logits, const void* gt, int gt_bytes, int B, long long V,
                         unsigned long long* out3b, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- multi-class evaluation (csrc/evalc.hip)
+ * The all-class form of the evaluator above (code/utils/test_3d_patch.py:334-336 computes the whole softmax; :337-347 keep class 1):
+ * every window adds its C-way softmax, C in 2..8, to score, fp32 class-major (C, D0, D1, D2), and 1 to cnt (D0, D1, D2); logits
+ * (n_patches, p0, p1, p2, C) fp32, n_patches <= 64.  Voxel-centric, fixed window order, no atomics.  The grid covers the box
+ * [box_lo, box_hi) only (host ints; the bounding box of the chunk's windows, inside the volume); a voxel of the box that no window
+ * of the chunk covers keeps its score and cnt. */
+int dycon_sw_accumulate_all(const float* logits, int C, int n_patches, int p0, int p1, int p2, const int* origins_dev,
+                            float* score, float* cnt, int D0, int D1, int D2, const int* box_lo, const int* box_hi,
+                            dycon_stream_t stream);
+/* p_c = score_c / cnt (code/utils/test_3d_patch.py:344), label = argmax_c p_c with the lowest index on ties (np.argmax); prob
+ * (class-major (C, n), may be NULL, may be score itself) = p */
+int dycon_sw_finalize_argmax(const float* score, const float* cnt, int C, long long n, uint8_t* label, float* prob,
+                             dycon_stream_t stream);
+/* label = argmax_c logits[v, c] of (nvox, C) fp32 logits, lowest index on ties: torch.argmax(softmax(outputs), dim=1) of
+ * code/train_DyCON_ISLES22.py:364-366 */
+int dycon_argmax_labels(const float* logits, int C, long long nvox, uint8_t* label, dycon_stream_t stream);
+/* out (device, C*C + 1 counters, caller zeroes): out[p*C + g] += voxels with pred == p and gt == g, the counts behind the per-class
+ * Dice of code/utils/metrics.py:14-27 (cal_dice) and medpy's dc / jc per class (code/utils/test_3d_patch.py:496-508); out[C*C] +=
+ * voxels whose pred or gt lies outside [0, C), counted nowhere else.  gt: uint8 (gt_bytes 1) or int64 (8). */
+int dycon_class_confusion(const uint8_t* pred, const void* gt, int gt_bytes, long long n, int C, unsigned long long* out,
+                          dycon_stream_t stream);
+/* The same per sample, out (B, C*C + 1), with pred = argmax_c logits read straight from the (B, V, C) fp32 logits: the C-class
+ * form of dycon_batch_overlap (code/train_DyCON_BraTS19.py:385-392) */
+int dycon_batch_class_confusion(const float* logits, const void* gt, int gt_bytes, int B, long long V, int C,
+                                unsigned long long* out, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
  * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
  * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
