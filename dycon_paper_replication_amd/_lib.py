@@ -141,6 +141,9 @@ SIGNATURES = {
     "dycon_argmax_labels": (I, [P, I, L, P, P]),
     "dycon_class_confusion": (I, [P, P, I, L, I, P, P]),
     "dycon_batch_class_confusion": (I, [P, P, I, I, L, I, P, P]),
+    "dycon_surface_workspace": (Z, [I, I, I, I]),
+    "dycon_surface_hist": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, Z, P]),
+    "dycon_surface_metrics": (I, [P, P, I, I, C.c_double, P, P]),
     "dycon_simhist_workspace": (Z, [I, I, I, I]),
     "dycon_simhist": (I, [P, P, I, I, I, I, F, I, P, P, P, P, Z, P]),
     "dycon_tap_gather": (I, [P, P, I, I, I, I, I, I, P, I, P]),

@@ -9,3 +9,5 @@ test_3d_patch.test_single_case = sliding_window.test_single_case
 
 # the all-class evaluator and the per-class metrics come beside it under names of their own and rebind nothing
 from . import eval_classes  # noqa: E402,F401
+from . import surface  # noqa: E402,F401
+from . import surface_eval  # noqa: E402,F401

@@ -4,7 +4,8 @@
 the reference-compatible evaluator.  The functions here are the standard multi-class form it was derived from, under names of their
 own: every window adds its whole C-way softmax to a class-major (C, w, h, d) score map, the label map is the argmax of the averaged
 scores (lowest index on ties, as ``np.argmax``), and Dice / Jaccard are taken per foreground class from one C x C confusion matrix
-counted on the device.  HD95 / ASD stay on the host (``test_3d_patch._surface_distances``), one binary pair per class.
+counted on the device.  HD95 / ASD stay on the host (``test_3d_patch._surface_distances``), one binary pair per class, unless
+``device_surface=True`` asks for the device form (``utils/surface.py``: all classes of a case in one set of launches).
 
     test_single_case_classes(model, image, stride_xy, stride_z, patch_size)     -> (label_map, score_map) as numpy
     single_case_classes_device(...)                                             -> the same as device tensors, no host copies
@@ -22,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import metrics
+from . import metrics, surface
 from .test_3d_patch import _read_case, _surface_distances, _windows
 
 
@@ -145,20 +146,26 @@ def metrics_from_confusion(conf):
     return np.array([_dc_jc(int(conf[c].sum()), int(conf[:, c].sum()), int(conf[c, c])) for c in range(1, conf.shape[0])])
 
 
-def calculate_metric_perclass(pred, gt, num_classes):
+def calculate_metric_perclass(pred, gt, num_classes, device_surface=False):
     """(C-1, 4) array of (dice, jaccard, hd95, asd), one row per foreground class, each `calculate_metric_percase(pred == c, gt == c)`
     (code/utils/test_3d_patch.py:496-508) with the reference's conventions for empty masks: a class the prediction does not contain
     gives (0, 0, 0, 0) (:268-271), a class absent from the ground truth hd95 = asd = 0 (:500-503).  Dice and Jaccard come from the
-    device counts; the surface distances run on the host."""
+    device counts; the surface distances run on the host, or, with device_surface=True, for all foreground classes in one
+    `surface.surface_metrics` call on the label maps (unit voxel spacing, csrc/surface.hip)."""
     conf = confusion_counts(pred, gt, num_classes).cpu().numpy()
     out = np.zeros((conf.shape[0] - 1, 4))
-    p_host = g_host = None
+    p_host = g_host = dev = None
     for c in range(1, conf.shape[0]):
         n_p, n_g = int(conf[c].sum()), int(conf[:, c].sum())
         if n_p == 0:
             continue
         out[c - 1, :2] = _dc_jc(n_p, n_g, int(conf[c, c]))
         if n_g == 0:
+            continue
+        if device_surface:
+            if dev is None:
+                dev = surface.surface_metrics(pred, gt, classes=(1, conf.shape[0] - 1)).cpu().numpy()
+            out[c - 1, 2:] = dev[c - 1, 0], dev[c - 1, 1]
             continue
         if p_host is None:
             p_host = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred)
@@ -169,10 +176,11 @@ def calculate_metric_perclass(pred, gt, num_classes):
 
 
 def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
-                          preproc_fn=None, test_save_path=None, label_key="label"):
+                          preproc_fn=None, test_save_path=None, label_key="label", device_surface=False):
     """`test_all_case` (code/utils/test_3d_patch.py:251-291) with the all-class evaluator: cases as there; returns the mean (C-1, 4)
     (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  There is no `nms`:
-    the largest component of a multi-class map is not defined by the reference."""
+    the largest component of a multi-class map is not defined by the reference.  device_surface is passed to
+    `calculate_metric_perclass`."""
     total = np.zeros((num_classes - 1, 4))
     n = 0
     for case in cases:
@@ -182,7 +190,7 @@ def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), st
         pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
         if score.shape[0] != num_classes:
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
-        m = calculate_metric_perclass(pred, np.asarray(label), num_classes)
+        m = calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface)
         if metric_detail:
             for c, row in enumerate(m, 1):
                 print("%02d, class %d,\t%.5f, %.5f, %.5f, %.5f" % ((n, c) + tuple(row)))

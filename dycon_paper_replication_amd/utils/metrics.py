@@ -7,7 +7,9 @@ of the binary volumes plus two distance transforms per sample: more host time th
     without a host sync;
   * `compute_hd95` keeps the reference's semantics (max_dist for an empty mask) on scipy ("parity unpinned": medpy absent);
   * `AsyncTrainMetrics` takes it off the critical path: every `every`-th iteration the binary maps are copied to pinned memory
-    asynchronously and a worker thread computes HD95 while the GPU trains on.
+    asynchronously and a worker thread computes HD95 while the GPU trains on;
+  * `compute_hd95_device` and `AsyncTrainMetrics(on_device=True)` are the opt-in device form (utils/surface.py, csrc/surface.hip):
+    exact surface distances for unit spacing, a device tensor back, no host copy, no worker.
 
 Those names are 2-class and refuse another width.  For 2..8 classes, under names of their own: `class_dice_from_logits` (per sample
 and foreground class, from one confusion count over the logits, csrc/evalc.hip), `AsyncClassTrainMetrics`, the device path of
@@ -22,6 +24,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import surface
 from .test_3d_patch import _surface_distances
 
 
@@ -191,22 +194,38 @@ def compute_hd95(pred, target, max_dist):
     return scores
 
 
+def compute_hd95_device(pred, target, max_dist):
+    """`compute_hd95` on the device (utils/surface.py; unit voxel spacing): pred / target are (B, X, Y, Z) binary volumes, numpy or
+    CUDA; returns a (B,) float64 device tensor.  A sample where either mask is empty gets max_dist (utils/metrics.py:117-118),
+    selected on the device: no host copy and no sync."""
+    if len(pred.shape) != 4:
+        raise ValueError(f"compute_hd95_device takes (B, X, Y, Z) volumes, got {tuple(pred.shape)}")
+    hd = surface.surface_metrics(pred, target)[:, 0]
+    return torch.where(torch.isnan(hd), torch.full_like(hd, float(max_dist)), hd)     # NaN = an empty border = an empty mask
+
+
 class AsyncTrainMetrics:
     """Per-iteration Dice on the device, HD95 every `every` iterations on a worker thread.
 
         m = AsyncTrainMetrics(every=50)
         m.update(iter_num, out["s_logits"], label)     # never blocks on the GPU
         m.latest()  ->  {"iter": .., "dice": tensor (device), "hd95": (iter, mean) or None}
+
+    With `on_device=True` there is no worker thread, no pinned buffer and no queue: every `every`-th `update` enqueues
+    `compute_hd95_device` on the current stream and "hd95" is (iter, 0-dim device tensor of the batch mean).
     """
 
-    def __init__(self, every=50):
+    def __init__(self, every=50, on_device=False):
         self.every = every
-        self._q = queue.Queue(maxsize=2)
+        self.on_device = bool(on_device)
         self._hd = None
         self._dice = None
         self._iter = -1
-        self._t = threading.Thread(target=self._work, daemon=True)
-        self._t.start()
+        self._q = self._t = None
+        if not self.on_device:
+            self._q = queue.Queue(maxsize=2)
+            self._t = threading.Thread(target=self._work, daemon=True)
+            self._t.start()
 
     def _work(self):
         while True:
@@ -221,6 +240,11 @@ class AsyncTrainMetrics:
         lg = _two_class_ndhwc(logits)
         self._iter = iter_num
         self._dice = batch_dice_from_logits(logits, labels)
+        if self.on_device:
+            if self.every and iter_num % self.every == 0:
+                pred = (lg[..., 1] > lg[..., 0]).to(torch.uint8)
+                self._hd = (iter_num, compute_hd95_device(pred, labels, float(np.linalg.norm(pred.shape[1:]))).mean())
+            return
         if self.every and iter_num % self.every == 0 and not self._q.full():
             pred = (lg[..., 1] > lg[..., 0]).to(torch.uint8)
             ph = torch.empty(pred.shape, dtype=torch.uint8).pin_memory()
@@ -235,7 +259,8 @@ class AsyncTrainMetrics:
         return {"iter": self._iter, "dice": self._dice, "hd95": self._hd}
 
     def close(self):
-        self._q.put(None)
+        if self._q is not None:
+            self._q.put(None)
 
 
 class AsyncClassTrainMetrics(AsyncTrainMetrics):
@@ -246,6 +271,15 @@ class AsyncClassTrainMetrics(AsyncTrainMetrics):
         lg = _class_ndhwc(logits, labels).contiguous().float()
         self._iter = iter_num
         self._dice = _class_dice_ndhwc(lg, labels)
+        if self.on_device:
+            if self.every and iter_num % self.every == 0:
+                arg = torch.empty(labels.shape, dtype=torch.uint8, device=lg.device)
+                _lib.call("dycon_argmax_labels", lg.data_ptr(), lg.shape[-1], arg.numel(), arg.data_ptr(),
+                          torch.cuda.current_stream().cuda_stream)
+                hd = surface.surface_metrics(arg, labels, classes=(1, 1))[:, 0]         # class 1 straight from the label maps
+                max_dist = float(np.linalg.norm(labels.shape[1:]))
+                self._hd = (iter_num, torch.where(torch.isnan(hd), torch.full_like(hd, max_dist), hd).mean())
+            return
         if self.every and iter_num % self.every == 0 and not self._q.full():
             arg = torch.empty(labels.shape, dtype=torch.uint8, device=lg.device)
             _lib.call("dycon_argmax_labels", lg.data_ptr(), lg.shape[-1], arg.numel(), arg.data_ptr(),

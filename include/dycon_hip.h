@@ -611,6 +611,23 @@ int dycon_class_confusion(const uint8_t* pred, const void* gt, int gt_bytes, lon
 int dycon_batch_class_confusion(const float* logits, const void* gt, int gt_bytes, int B, long long V, int C,
                                 unsigned long long* out, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- surface distances, unit voxel spacing (csrc/surface.hip)
+ * HD95 / ASD of medpy.metric.binary (code/utils/test_3d_patch.py:496-508, code/utils/metrics.py:112-131) without a host copy.  A call
+ * handles S = n_vol * n_cls pairs; pair s = v * n_cls + k reads volume v of a (prediction, uint8: a_bytes 1) and of b (ground truth,
+ * uint8 or int64: b_bytes 1 or 8), each (n_vol, X, Y, Z) with Z innermost and every axis in 1..512.  Membership is voxel != 0 when
+ * cls_lo == 0 (then n_cls must be 1), voxel == cls_lo + k otherwise.  Per pair and mask: border = m & ~erode6(m) with the outside of
+ * the volume as background, then the exact int32 squared Euclidean distance transform of the border set in three separable passes.
+ * hist (S, 2, nbins) unsigned int, nbins = (X-1)^2 + (Y-1)^2 + (Z-1)^2 + 1, zeroed by the call: hist[s][0][d] = border voxels of a at
+ * squared distance d from the border of b, hist[s][1] the other direction; a direction whose target border is empty stays zero.
+ * nborder (S, 2) = |border(a)|, |border(b)|.  Integer atomics only: the same bits on every run.  workspace: 2 int32 volumes per pair. */
+size_t dycon_surface_workspace(int S, int X, int Y, int Z);
+int dycon_surface_hist(const void* a, int a_bytes, const void* b, int b_bytes, int n_vol, int cls_lo, int n_cls, int X, int Y, int Z,
+                       unsigned int* hist, unsigned int* nborder, void* workspace, size_t ws_bytes, dycon_stream_t stream);
+/* out (S, 5) double = { percentile q of sqrt(bin) over both directions (np.percentile's default linear rule), mean a->b, mean b->a,
+ * |border(a)|, |border(b)| }, fp64 in a fixed order, one workgroup per pair; the first three are NaN when either border is empty */
+int dycon_surface_metrics(const unsigned int* hist, const unsigned int* nborder, int S, int nbins, double q, double* out,
+                          dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
  * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
  * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
