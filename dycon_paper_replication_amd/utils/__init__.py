@@ -11,3 +11,5 @@ test_3d_patch.test_single_case = sliding_window.test_single_case
 from . import eval_classes  # noqa: E402,F401
 from . import surface  # noqa: E402,F401
 from . import surface_eval  # noqa: E402,F401
+from . import components  # noqa: E402,F401
+from . import device_eval  # noqa: E402,F401

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import metrics, surface
+from . import components, metrics, surface
 from .test_3d_patch import _read_case, _surface_distances, _windows
 
 
@@ -176,11 +176,12 @@ def calculate_metric_perclass(pred, gt, num_classes, device_surface=False):
 
 
 def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
-                          preproc_fn=None, test_save_path=None, label_key="label", device_surface=False):
+                          preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, nms=0):
     """`test_all_case` (code/utils/test_3d_patch.py:251-291) with the all-class evaluator: cases as there; returns the mean (C-1, 4)
-    (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  There is no `nms`:
-    the largest component of a multi-class map is not defined by the reference.  device_surface is passed to
-    `calculate_metric_perclass`."""
+    (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  device_surface is
+    passed to `calculate_metric_perclass`.  The reference defines `nms` for the class-1 map only (:19-26, :266-267); `nms` here is
+    its per-class extension: each foreground class of the prediction keeps its largest component
+    (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is."""
     total = np.zeros((num_classes - 1, 4))
     n = 0
     for case in cases:
@@ -190,6 +191,8 @@ def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), st
         pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
         if score.shape[0] != num_classes:
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
+        if nms:
+            pred = components.largest_component_per_class(pred, num_classes)
         m = calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface)
         if metric_detail:
             for c, row in enumerate(m, 1):

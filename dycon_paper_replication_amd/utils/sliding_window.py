@@ -19,19 +19,14 @@ _two_class_single_case = _two.test_single_case        # the function written in 
 assert _two_class_single_case.__module__ == _two.__name__
 
 
-def test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=1, batch_size=4, device=None):
-    """image: (w, h, d) numpy array or tensor.  Returns (label_map int64 (w,h,d), score_map float32 (num_classes,w,h,d)) as numpy,
-    like the reference; the class-1 probability fills every channel of score_map (the reference's broadcast, :338-339), and
-    label_map = score > 0.5 (:345).  The model may have 2..8 classes.
-
-    ``batch_size`` windows go through the network per launch sequence (the reference runs them one by one)."""
-    if getattr(model, "n_classes", None) == 2:
-        return _two_class_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, batch_size=batch_size,
-                                      device=device)
+def single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
+    """The device-resident form of `test_single_case`: (label uint8 (w, h, d), prob float32 (w, h, d)) as CUDA tensors, the same
+    launches in the same order without the copies to the host.  label = prob > 0.5 of the class-1 probability; 2..8 classes.  image:
+    (w, h, d) numpy array or tensor."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     if dev.type != "cuda":
-        raise RuntimeError("test_single_case runs on the MI355X only: move the model to 'cuda'")
-    img = torch.as_tensor(np.asarray(image), dtype=torch.float32)
+        raise RuntimeError("the sliding window runs on the MI355X only: move the model to 'cuda'")
+    img = (image if torch.is_tensor(image) else torch.as_tensor(np.asarray(image))).to(dtype=torch.float32)
     w, h, d = img.shape
     pads = []
     for size, p in zip((w, h, d), patch_size):                 # :297-316: centre-pad volumes smaller than the window
@@ -80,6 +75,19 @@ def test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=
     if add_pad:
         sl = tuple(slice(lo, lo + n) for (lo, _), n in zip(pads, (w, h, d)))
         label, prob = label[sl], prob[sl]
+    return label, prob
+
+
+def test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=1, batch_size=4, device=None):
+    """image: (w, h, d) numpy array or tensor.  Returns (label_map int64 (w,h,d), score_map float32 (num_classes,w,h,d)) as numpy,
+    like the reference; the class-1 probability fills every channel of score_map (the reference's broadcast, :338-339), and
+    label_map = score > 0.5 (:345).  The model may have 2..8 classes.
+
+    ``batch_size`` windows go through the network per launch sequence (the reference runs them one by one)."""
+    if getattr(model, "n_classes", None) == 2:
+        return _two_class_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, batch_size=batch_size,
+                                      device=device)
+    label, prob = single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, device=device)
     label_map = label.cpu().numpy().astype(np.int64)
     score_map = np.broadcast_to(prob.cpu().numpy()[None], (num_classes,) + label_map.shape).copy()
     return label_map, score_map

@@ -628,6 +628,29 @@ int dycon_surface_hist(const void* a, int a_bytes, const void* b, int b_bytes, i
 int dycon_surface_metrics(const unsigned int* hist, const unsigned int* nborder, int S, int nbins, double q, double* out,
                           dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- 3-D connected components (csrc/components.hip)
+ * The `nms` step of code/utils/test_3d_patch.py:19-26 (skimage.measure.label + the largest component) without a host copy.  vol:
+ * (n_vol, X, Y, Z) uint8 or int64 (vol_bytes 1 or 8), Z innermost, every axis in 1..512, at most 65535 volumes and 2^31 - 1 voxels per
+ * call.  connectivity 1, 2, 3 = 6, 18, 26 neighbours; neighbours never cross a face of a volume or the volumes of a batch.
+ *   roots  : by_value == 0: a voxel is foreground when non-zero; by_value != 0: neighbours are connected only when their values are
+ *            equal and lie in 1..255, every other value is background (skimage's rule on an integer map).  root (n_vol, X, Y, Z) int32
+ *            = 0 for background, else 1 + the smallest linear index (x*Y + y)*Z + z of the voxel's component.  Three launches.
+ *   labels : from root: labels int32 = 1..n in raster order of each component's first voxel (scipy.ndimage.label's numbering),
+ *            ncomp (n_vol) = n.  A hierarchical scan (chunk counts, one workgroup per volume, fix-up); no workgroup waits on another.
+ *   largest: from vol and its root: per volume (n_cls == 0, binary) or per volume and value 1..n_cls (n_cls >= 1, by value; other
+ *            values give 0) the component of the greatest voxel count, the smallest root among equals.  out uint8 = 1 (binary) or the
+ *            value on the winner, 0 elsewhere; win_size, win_root (n_vol, max(n_cls, 1)) int32, both 0 where there is no foreground.
+ * Integer atomics only (atomicMin on parents, atomicAdd on sizes, a 64-bit atomicMax on (size << 32) | (0xFFFFFFFF - root)): the
+ * same bits on every run.  No allocation, no host synchronisation, a fixed number of launches.  workspace: dycon_cc_workspace bytes
+ * (one int32 per voxel plus small tables), used by labels and largest. */
+size_t dycon_cc_workspace(int n_vol, int X, int Y, int Z);
+int dycon_cc_roots(const void* vol, int vol_bytes, int n_vol, int X, int Y, int Z, int connectivity, int by_value, int* root,
+                   dycon_stream_t stream);
+int dycon_cc_labels(const int* root, int n_vol, int X, int Y, int Z, int* labels, int* ncomp, void* workspace, size_t ws_bytes,
+                    dycon_stream_t stream);
+int dycon_cc_largest(const void* vol, int vol_bytes, const int* root, int n_vol, int X, int Y, int Z, int n_cls, uint8_t* out,
+                     int* win_size, int* win_root, void* workspace, size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
  * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
  * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
