@@ -6,7 +6,9 @@
 
 The transforms draw from ``np.random`` in the reference's call order, so a seeded run reproduces the reference's augmentation
 stream; they accept numpy arrays (the reference's DataLoader workers) and torch tensors alike -- on CUDA tensors crop / rot90 /
-flip are index operations on the device, which is how a whole volume cache in HBM (288 GB) is augmented without a host round trip.
+flip are per-sample torch index operations on the device.  Training from a whole volume cache in HBM (288 GB) without a host round
+trip is dataloaders/device_cache.py: DeviceVolumeCache + DeviceBatchLoader assemble a batch in one HIP launch, bit for bit what
+these transforms yield for the same np.random stream.
 h5py is not available in this image: the dataset class imports it lazily and is exercised only where the data lives.
 """
 from __future__ import annotations

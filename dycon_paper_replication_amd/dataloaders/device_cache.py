@@ -1,0 +1,268 @@
+"""Device-resident training data: the whole training set cached in HBM, batches assembled by one HIP launch.
+
+    DeviceVolumeCache(samples, device, pre, max_bytes)        every case once: images fp32, labels uint8, two arenas in HBM
+    draw_plan(shapes, indices, patch_size, rot_flip, center)  host: the crops / rotations / flips RandomCrop + RandomRotFlip would draw
+    apply_plan_host(plan, images, labels)                     host: numpy restatement of the kernel (the CPU-testable twin)
+    assemble_batch(cache, plan, out, label_dtype)             device: dycon_assemble_batch, one launch per 16 samples
+    DeviceBatchLoader(cache, batch_sampler, patch_size, ...)  iterates a batch sampler, yields {"image", "label"} device batches
+
+The training pipelines of the reference's three scripts are `[SagittalToAxial ->] RandomCrop -> RandomRotFlip -> ToTensor`
+(train_DyCON_BraTS19.py:238-242, train_DyCON_Pancreas.py:150-167, train_DyCON_ISLES22.py:165-190) in DataLoader worker processes.
+A conditional zero pad, a crop, a rotation by k * 90 degrees about the first two axes and a flip of axis 0 or 1 are gathers, so the
+kernel (csrc/datapath.hip) writes the (B, 1, w, h, d) batch and its labels straight from the cached volumes -- the padded array of
+the reference never exists, a source index outside the stored volume reads as 0.
+
+What is equal to what.  For a seeded ``np.random`` the loader yields, bit for bit, what
+``DataLoader(dataset_with_the_transform_chain, batch_sampler=..., num_workers=0)`` yields with the transforms of
+dataloaders/brats19.py: `draw_plan` consumes ``np.random`` exactly as RandomCrop then RandomRotFlip do for each index in order
+(three randint for the crop with bounds from the padded shape, then k, then the axis), between the batch sampler's own draws.
+The reference's multi-worker stream (num_workers=4, every worker with its own copy of the generator state) is not reproducible by
+anything, this loader included.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib, ops
+
+#: one output sample: the case, the crop origin in STORED coordinates (crop offset - pad: negative where the reference pads), the
+#: np.rot90 count, the flipped axis (-1: none) and the patch it belongs to
+PLAN_DTYPE = np.dtype([("case", "<i8"), ("origin", "<i4", (3,)), ("k", "<i4"), ("flip_axis", "<i4"), ("patch", "<i4", (3,))])
+
+# dycon_crop_job_t (include/dycon_hip.h), field for field
+_JOB_DTYPE = np.dtype([("image_off", "<i8"), ("label_off", "<i8"), ("X", "<i4"), ("Y", "<i4"), ("Z", "<i4"),
+                       ("ox", "<i4"), ("oy", "<i4"), ("oz", "<i4"), ("k", "<i4"), ("flip_axis", "<i4")], align=True)
+JOBS_PER_LAUNCH = 16           # DYCON_CROP_JOBS_MAX
+_ALIGN = 16                    # bytes: every case starts at a 16-byte-aligned offset of its arena
+
+
+def _host_label(label):
+    """labels as uint8: integers 0..255 in any integer / bool / float dtype (ISLES stores its mask as float64)"""
+    a = np.asarray(label)
+    if a.dtype == np.uint8:
+        return a
+    if a.dtype == np.bool_:
+        return a.astype(np.uint8)
+    if not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"labels must be integers in 0..255, got dtype {a.dtype}")
+    if a.size and not (a.min() >= 0 and a.max() <= 255):        # also rejects NaN
+        raise ValueError(f"labels must be integers in 0..255, got values in [{a.min()}, {a.max()}]")
+    u = a.astype(np.uint8)
+    if np.issubdtype(a.dtype, np.floating) and not np.array_equal(u, a):
+        raise ValueError("labels must be integers in 0..255, got non-integral values")
+    return u
+
+
+class DeviceVolumeCache:
+    """Every case of `samples` (an iterable of {"image", "label"} host arrays: a dataset of this package built with
+    ``transform=None`` qualifies) resident on `device`: images as fp32 in one arena, labels as uint8 in another, each case
+    C-contiguous at a 16-byte-aligned offset.
+
+    pre: an optional DETERMINISTIC transform applied on the host once per case before it is stored -- meant for
+    ``SagittalToAxial()``, so that the cached orientation is the one whose last axis the crop keeps contiguous.
+    max_bytes: upper bound of `nbytes`; exceeded -> ValueError before anything is allocated on the device.
+
+    The image is cast to fp32 at insertion.  ToTensor casts after the gathers (crop, rot90, flip and the zero pad move or insert
+    values, they compute none), and a cast applied to every element commutes with a gather, so the bits are the same.
+    Labels must be integers in 0..255 (any integer, bool or float dtype); anything else raises ValueError."""
+
+    def __init__(self, samples, device=None, pre=None, max_bytes=None):
+        self.device = torch.device("cuda" if device is None else device)
+        images, labels, self._shapes = [], [], []
+        img_off, lab_off, ni, nl = [], [], 0, 0
+        for s in samples:
+            if pre is not None:
+                s = pre(s)
+            img = np.ascontiguousarray(np.asarray(s["image"]), dtype=np.float32)
+            lab = np.ascontiguousarray(_host_label(s["label"]))
+            if img.ndim != 3 or img.shape != lab.shape:
+                raise ValueError(f"a case is a 3-D image with a label of its shape, got {img.shape} and {lab.shape}")
+            img_off.append(ni)
+            lab_off.append(nl)
+            ni += -(-img.size // (_ALIGN // 4)) * (_ALIGN // 4)
+            nl += -(-lab.size // _ALIGN) * _ALIGN
+            if max_bytes is not None and 4 * ni + nl > max_bytes:
+                raise ValueError(f"the cache needs more than max_bytes = {max_bytes} (at case {len(images)}: {4 * ni + nl} bytes)")
+            images.append(img)
+            labels.append(lab)
+            self._shapes.append(tuple(int(v) for v in img.shape))
+        if not images:
+            raise ValueError("no cases to cache")
+        self._nbytes = 4 * ni + nl
+        self._img_off = np.asarray(img_off, dtype=np.int64)
+        self._lab_off = np.asarray(lab_off, dtype=np.int64)
+        self._shape_arr = np.asarray(self._shapes, dtype=np.int32)
+        self.images = torch.zeros(ni, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(nl, dtype=torch.uint8, device=self.device)
+        for img, lab, oi, ol in zip(images, labels, img_off, lab_off):
+            self.images[oi:oi + img.size].copy_(torch.from_numpy(img.reshape(-1)))
+            self.labels[ol:ol + lab.size].copy_(torch.from_numpy(lab.reshape(-1)))
+
+    def __len__(self):
+        return len(self._shapes)
+
+    @property
+    def shapes(self):
+        """stored (X, Y, Z) of every case (after `pre`)"""
+        return list(self._shapes)
+
+    @property
+    def nbytes(self):
+        """bytes of the two arenas"""
+        return self._nbytes
+
+    def host_case(self, idx):
+        """(image fp32, label uint8) of one case as host arrays: what the kernel reads (tests, apply_plan_host)"""
+        n = int(np.prod(self._shapes[idx]))
+        oi, ol = int(self._img_off[idx]), int(self._lab_off[idx])
+        return (self.images[oi:oi + n].cpu().numpy().reshape(self._shapes[idx]),
+                self.labels[ol:ol + n].cpu().numpy().reshape(self._shapes[idx]))
+
+
+def _pads(shape, patch):
+    """_pad_to of dataloaders/brats19.py as the reference has it: as soon as ANY axis is <= the patch, ALL three axes are padded by
+    (size - shape)//2 + 3 per side, clamped at 0"""
+    if shape[0] <= patch[0] or shape[1] <= patch[1] or shape[2] <= patch[2]:
+        return tuple(max((patch[a] - shape[a]) // 2 + 3, 0) for a in range(3))
+    return (0, 0, 0)
+
+
+def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False):
+    """The plan of one batch: a PLAN_DTYPE record per entry of `indices` (case numbers into `shapes`).
+
+    Pure host code.  Consumes ``np.random`` exactly as ``RandomCrop(patch_size)`` followed by ``RandomRotFlip()`` do for each index
+    in order: three randint for the crop, bounds from the PADDED shape, then k, then the axis (rot_flip=False: the crop only,
+    k = 0, no flip).  center=True gives the CenterCrop origin and draws nothing.  An odd k with patch_size[0] != patch_size[1]
+    raises ValueError: the rotated crop would not have the patch's shape (the reference could not stack such a batch either)."""
+    patch = tuple(int(v) for v in patch_size)
+    if len(patch) != 3 or min(patch) <= 0:
+        raise ValueError(f"patch_size must be three positive sizes, got {patch_size}")
+    plan = np.zeros(len(indices), dtype=PLAN_DTYPE)
+    for n, idx in enumerate(indices):
+        shape = shapes[idx]
+        pad = _pads(shape, patch)
+        w, h, d = (shape[a] + 2 * pad[a] for a in range(3))
+        k, axis = 0, -1
+        if center:
+            w1, h1, d1 = (int(round((s - o) / 2.)) for s, o in zip((w, h, d), patch))
+        else:
+            w1 = np.random.randint(0, w - patch[0])
+            h1 = np.random.randint(0, h - patch[1])
+            d1 = np.random.randint(0, d - patch[2])
+            if rot_flip:
+                k = np.random.randint(0, 4)
+                axis = np.random.randint(0, 2)
+        if (k & 1) and patch[0] != patch[1]:
+            raise ValueError(f"rot90 by k = {k} of a {patch[0]} x {patch[1]} crop does not give a {patch[0]} x {patch[1]} patch")
+        plan[n] = (idx, (w1 - pad[0], h1 - pad[1], d1 - pad[2]), k, axis, patch)
+    return plan
+
+
+def _check_plan(plan, ncases):
+    """-> the patch of a well-formed plan; ValueError otherwise (the library rejects the same things: this names them earlier)"""
+    plan = np.asarray(plan)
+    if plan.dtype != PLAN_DTYPE or plan.ndim != 1 or len(plan) == 0:
+        raise ValueError("a plan is a non-empty 1-D array of PLAN_DTYPE records (draw_plan)")
+    patch = tuple(int(v) for v in plan["patch"][0])
+    if (plan["patch"] != plan["patch"][0]).any() or min(patch) <= 0:
+        raise ValueError("all samples of a batch share one positive patch size")
+    if plan["case"].min() < 0 or plan["case"].max() >= ncases:
+        raise ValueError(f"plan names case {plan['case'].max()} of {ncases}")
+    if plan["k"].min() < 0 or plan["k"].max() > 3 or plan["flip_axis"].min() < -1 or plan["flip_axis"].max() > 1:
+        raise ValueError("k must be in 0..3 and flip_axis in {-1, 0, 1}")
+    if patch[0] != patch[1] and (plan["k"] & 1).any():
+        raise ValueError(f"an odd k needs a square patch in the first two axes, got {patch[0]} x {patch[1]}")
+    return patch
+
+
+def apply_plan_host(plan, images, labels):
+    """What the kernel does with a plan, in numpy: images / labels are the per-case host arrays in the CACHED orientation.
+    -> {"image": (B, 1, w, h, d) float32, "label": (B, w, h, d) uint8} host arrays."""
+    P0, P1, P2 = _check_plan(plan, len(images))
+    B = len(plan)
+    out_i = np.zeros((B, 1, P0, P1, P2), dtype=np.float32)
+    out_l = np.zeros((B, P0, P1, P2), dtype=np.uint8)
+    i, j = np.meshgrid(np.arange(P0), np.arange(P1), indexing="ij")
+    z = np.arange(P2)
+    for n, rec in enumerate(plan):
+        img, lab = np.asarray(images[rec["case"]]), np.asarray(labels[rec["case"]])
+        X, Y, Z = img.shape
+        fi = P0 - 1 - i if rec["flip_axis"] == 0 else i          # undo the flip ...
+        fj = P1 - 1 - j if rec["flip_axis"] == 1 else j
+        a, b = {0: (fi, fj), 1: (fj, P1 - 1 - fi), 2: (P0 - 1 - fi, P1 - 1 - fj), 3: (P0 - 1 - fj, fi)}[int(rec["k"])]   # ... and the rot90
+        sx, sy, sz = rec["origin"][0] + a, rec["origin"][1] + b, rec["origin"][2] + z
+        ok = ((sx >= 0) & (sx < X) & (sy >= 0) & (sy < Y))[:, :, None] & ((sz >= 0) & (sz < Z))[None, None, :]
+        cx, cy, cz = np.clip(sx, 0, X - 1)[:, :, None], np.clip(sy, 0, Y - 1)[:, :, None], np.clip(sz, 0, Z - 1)[None, None, :]
+        out_i[n, 0] = np.where(ok, img[cx, cy, cz], 0).astype(np.float32)
+        out_l[n] = np.where(ok, lab[cx, cy, cz], 0).astype(np.uint8)
+    return {"image": out_i, "label": out_l}
+
+
+def assemble_batch(cache, plan, out=None, label_dtype=torch.uint8):
+    """-> {"image": (B, 1, w, h, d) float32, "label": (B, w, h, d) uint8 | int64} on the cache's device, enqueued on the current
+    stream: one launch of dycon_assemble_batch per 16 samples, no allocation when `out` (a dict of such tensors) is given, no host
+    synchronisation.  There is no host fallback: a cache that is not on a GPU raises."""
+    P0, P1, P2 = _check_plan(plan, len(cache))
+    if label_dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"label_dtype must be torch.uint8 or torch.int64, got {label_dtype}")
+    if cache.device.type != "cuda":
+        raise _lib.DyconLibraryError("assemble_batch runs on the GPU only (the cache is on %s)" % cache.device)
+    B = len(plan)
+    if out is None:
+        out = {"image": torch.empty((B, 1, P0, P1, P2), dtype=torch.float32, device=cache.images.device),
+               "label": torch.empty((B, P0, P1, P2), dtype=label_dtype, device=cache.images.device)}
+    image, label = out["image"], out["label"]
+    if not (tuple(image.shape) == (B, 1, P0, P1, P2) and image.dtype == torch.float32 and tuple(label.shape) == (B, P0, P1, P2)
+            and label.dtype == label_dtype and image.is_contiguous() and label.is_contiguous()
+            and image.device == cache.images.device and label.device == cache.images.device):
+        raise ValueError("out: contiguous (B, 1, w, h, d) float32 and (B, w, h, d) label_dtype tensors on the cache's device")
+    case = plan["case"]
+    jobs = np.empty(B, dtype=_JOB_DTYPE)
+    jobs["image_off"], jobs["label_off"] = cache._img_off[case], cache._lab_off[case]
+    jobs["X"], jobs["Y"], jobs["Z"] = cache._shape_arr[case].T
+    jobs["ox"], jobs["oy"], jobs["oz"] = plan["origin"].T
+    jobs["k"], jobs["flip_axis"] = plan["k"], plan["flip_axis"]
+    vox, lb = P0 * P1 * P2, label.element_size()
+    stream = ops._s()
+    for n0 in range(0, B, JOBS_PER_LAUNCH):
+        n = min(JOBS_PER_LAUNCH, B - n0)
+        _lib.call("dycon_assemble_batch", cache.images.data_ptr(), cache.labels.data_ptr(), jobs.ctypes.data + n0 * _JOB_DTYPE.itemsize,
+                  n, P0, P1, P2, image.data_ptr() + 4 * vox * n0, label.data_ptr() + lb * vox * n0, lb, stream)
+    return out
+
+
+class DeviceBatchLoader:
+    """Iterating walks `batch_sampler` (any sampler of this package: TwoStreamBatchSampler, ThreeStreamBatchSampler, ...): for each
+    batch of case indices the plan is drawn (draw_plan) and the batch assembled on the current stream into a ring of TWO output
+    buffer pairs, so a yielded batch stays valid until the next-but-one is produced.  ``DyconTrainer.step(b["image"], b["label"])``
+    takes the tensors as they are.
+
+    For a seeded ``np.random`` the batches equal those of ``DataLoader(dataset, batch_sampler=batch_sampler, num_workers=0)`` with
+    ``transform = Compose([RandomCrop(patch_size), RandomRotFlip(), ToTensor()])`` bit for bit (label_dtype=torch.int64 for
+    ToTensor's dtype; `pre=SagittalToAxial()` on the cache for the BraTS chain; rot_flip=False leaves RandomRotFlip out).  The
+    reference's multi-worker stream is not reproducible by anything."""
+
+    def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8):
+        self.cache, self.batch_sampler, self.rot_flip, self.label_dtype = cache, batch_sampler, rot_flip, label_dtype
+        self.patch_size = tuple(int(v) for v in patch_size)
+        self._ring, self._n = [None, None], 0
+
+    def __len__(self):
+        return len(self.batch_sampler)
+
+    def plans(self):
+        """the host side of an epoch on its own: the plan of every batch, in order (draws as iterating the loader does)"""
+        shapes = self.cache.shapes
+        for batch in self.batch_sampler:
+            yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip)
+
+    def __iter__(self):
+        for plan in self.plans():
+            slot = self._n & 1
+            self._n += 1
+            buf = self._ring[slot]
+            if buf is None or buf["image"].shape[0] != len(plan):
+                buf = None
+            self._ring[slot] = buf = assemble_batch(self.cache, plan, out=buf, label_dtype=self.label_dtype)
+            yield buf

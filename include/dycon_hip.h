@@ -696,6 +696,30 @@ int dycon_small_gemm(const float* a, long long sar, long long sai, const float* 
                      long long ldc, int I, int J, int R, int accumulate, dycon_stream_t stream);
 int dycon_copy_segments(const float* const* src_host, float* const* dst_host, const int* n_host, int nseg, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- training batches from a volume cache in HBM
+ * (dataloaders/device_cache.py; the reference's RandomCrop -> RandomRotFlip -> ToTensor, code/dataloaders/brats19.py:198-283)
+ * One launch writes out_image (njobs, 1, P0, P1, P2) fp32 and out_label (njobs, P0, P1, P2) uint8 (label_bytes 1) or int64
+ * (label_bytes 8) from cached cases: `images` (fp32) and `labels` (uint8) are arenas, a case of stored shape (X, Y, Z) lies
+ * C-contiguous at element offsets image_off / label_off.  Output sample n is
+ *     flip(rot90(padded[ox+pad : ox+pad+P0, oy+pad : .., oz+pad : ..], k, axes (0, 1)), flip_axis)      (numpy semantics)
+ * with the zero pad never materialised: (ox, oy, oz) is the crop origin in STORED coordinates (crop offset - pad, may be
+ * negative) and every source index outside [0,X) x [0,Y) x [0,Z) reads as 0, image and label alike.  flip_axis -1: no flip.
+ * jobs_host: njobs (1..DYCON_CROP_JOBS_MAX) descriptors in host memory, read at call time and passed to the kernel in its
+ * arguments (nothing has to outlive the call).  The caller guarantees that every case lies inside its arena.  Rejected before
+ * any launch: njobs out of range, a non-positive patch axis, k outside 0..3, flip_axis outside {-1, 0, 1}, an odd k with
+ * P0 != P1 (the rotated crop would not have the patch's shape).  16-byte stores when P2 % 4 == 0 and the outputs are 16-byte
+ * aligned, element stores otherwise; the source side assumes no alignment.  A pure gather: bitwise reproducible. */
+#define DYCON_CROP_JOBS_MAX 16
+typedef struct {
+    long long image_off, label_off; /* element offsets of the case in the two arenas */
+    int X, Y, Z;                    /* stored shape */
+    int ox, oy, oz;                 /* crop origin, stored coordinates */
+    int k;                          /* np.rot90 count, 0..3 */
+    int flip_axis;                  /* -1 | 0 | 1 */
+} dycon_crop_job_t;
+int dycon_assemble_batch(const float* images, const uint8_t* labels, const dycon_crop_job_t* jobs_host, int njobs, int P0, int P1,
+                         int P2, float* out_image, void* out_label, int label_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
