@@ -144,6 +144,8 @@ SIGNATURES = {
     "dycon_surface_workspace": (Z, [I, I, I, I]),
     "dycon_surface_hist": (I, [P, I, P, I, I, I, I, I, I, I, P, P, P, Z, P]),
     "dycon_surface_metrics": (I, [P, P, I, I, C.c_double, P, P]),
+    "dycon_surface_spaced_workspace": (Z, [I, I, I, I]),
+    "dycon_surface_spaced_metrics": (I, [P, I, P, I, I, I, I, I, I, I, P, I, C.c_double, P, P, Z, P]),
     "dycon_cc_workspace": (Z, [I, I, I, I]),
     "dycon_cc_roots": (I, [P, I, I, I, I, I, I, I, P, P]),
     "dycon_cc_labels": (I, [P, I, I, I, I, P, P, P, Z, P]),

@@ -7,7 +7,10 @@ The functions take the reference's names, arguments and defaults as ``utils/surf
 device: per case the host sends the image and the ground truth and reads back one "prediction is empty" flag, three overlap
 counts and, unless the ground truth is empty, one row of surface metrics.  The convention for an empty prediction, (0, 0, 0, 0),
 and ``performance.txt`` are those of ``test_3d_patch.test_all_case`` (:251-291).  Unit voxel spacing, as everywhere in the
-reference's evaluators.
+reference's evaluators, unless a case is given as ``(image, label, spacing)``: then HD95 / ASD of that case are in the units of its
+spacing (utils/surface.py, csrc/surface_spacing.hip).  The parameter lists stay those of ``utils/test_3d_patch.py``
+(tests/test_components_cpu.py pins them), so there is no ``voxelspacing=`` / ``connectivity=`` keyword here;
+``surface_eval.test_all_case(..., device_surface=True)`` has both.
 
     test_all_case(model, cases, num_classes, ..., nms=0)
     test_all_case_BraTS19 / _Pancreas / _ISLES22(..., nms=0)
@@ -17,7 +20,6 @@ from __future__ import annotations
 import numpy as np
 
 from . import components, sliding_window, surface_eval
-from . import test_3d_patch as _host
 
 
 def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
@@ -26,7 +28,7 @@ def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=
     total = np.zeros(4)
     n = 0
     for case in cases:
-        image, label = _host._read_case(case, label_key)
+        image, label, spacing = surface_eval.read_case(case, label_key)
         if preproc_fn is not None:
             image = preproc_fn(image)
         pred, _ = sliding_window.single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
@@ -35,7 +37,7 @@ def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=
         if not bool(pred.any()):                               # one flag read back; the empty-prediction convention of :268-271
             m = (0.0, 0.0, 0.0, 0.0)
         else:
-            m = surface_eval.calculate_metric_percase(pred, np.asarray(label), device_surface=True)
+            m = surface_eval.calculate_metric_percase(pred, np.asarray(label), device_surface=True, voxelspacing=spacing)
         if metric_detail:
             print("%02d,\t%.5f, %.5f, %.5f, %.5f" % ((n,) + tuple(m)))
         total += np.asarray(m)

@@ -146,12 +146,14 @@ def metrics_from_confusion(conf):
     return np.array([_dc_jc(int(conf[c].sum()), int(conf[:, c].sum()), int(conf[c, c])) for c in range(1, conf.shape[0])])
 
 
-def calculate_metric_perclass(pred, gt, num_classes, device_surface=False):
+def calculate_metric_perclass(pred, gt, num_classes, device_surface=False, voxelspacing=None, connectivity=1):
     """(C-1, 4) array of (dice, jaccard, hd95, asd), one row per foreground class, each `calculate_metric_percase(pred == c, gt == c)`
     (code/utils/test_3d_patch.py:496-508) with the reference's conventions for empty masks: a class the prediction does not contain
     gives (0, 0, 0, 0) (:268-271), a class absent from the ground truth hd95 = asd = 0 (:500-503).  Dice and Jaccard come from the
     device counts; the surface distances run on the host, or, with device_surface=True, for all foreground classes in one
-    `surface.surface_metrics` call on the label maps (unit voxel spacing, csrc/surface.hip)."""
+    `surface.surface_metrics` call on the label maps.  voxelspacing / connectivity are medpy's arguments of hd95 / asd, passed to
+    whichever of the two computes the distances; the defaults are unit spacing and 6-neighbour borders."""
+    spacing, connectivity = surface.normalise_spacing(voxelspacing, connectivity)
     conf = confusion_counts(pred, gt, num_classes).cpu().numpy()
     out = np.zeros((conf.shape[0] - 1, 4))
     p_host = g_host = dev = None
@@ -164,28 +166,36 @@ def calculate_metric_perclass(pred, gt, num_classes, device_surface=False):
             continue
         if device_surface:
             if dev is None:
-                dev = surface.surface_metrics(pred, gt, classes=(1, conf.shape[0] - 1)).cpu().numpy()
+                dev = surface.surface_metrics(pred, gt, classes=(1, conf.shape[0] - 1), voxelspacing=spacing,
+                                              connectivity=connectivity).cpu().numpy()
             out[c - 1, 2:] = dev[c - 1, 0], dev[c - 1, 1]
             continue
         if p_host is None:
             p_host = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred)
             g_host = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt)
-        hd1, hd2 = _surface_distances(p_host == c, g_host == c), _surface_distances(g_host == c, p_host == c)
+        hd1 = _surface_distances(p_host == c, g_host == c, spacing, connectivity)
+        hd2 = _surface_distances(g_host == c, p_host == c, spacing, connectivity)
         out[c - 1, 2:] = float(np.percentile(np.hstack((hd1, hd2)), 95)), float(hd1.mean())
     return out
 
 
 def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
-                          preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, nms=0):
+                          preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, nms=0, voxelspacing=None,
+                          connectivity=1):
     """`test_all_case` (code/utils/test_3d_patch.py:251-291) with the all-class evaluator: cases as there; returns the mean (C-1, 4)
     (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  device_surface is
     passed to `calculate_metric_perclass`.  The reference defines `nms` for the class-1 map only (:19-26, :266-267); `nms` here is
     its per-class extension: each foreground class of the prediction keeps its largest component
-    (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is."""
+    (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is.
+    voxelspacing / connectivity go to `calculate_metric_perclass`; a case given as (image, label, spacing) carries its own spacing."""
+    surface.normalise_spacing(voxelspacing, connectivity)
     total = np.zeros((num_classes - 1, 4))
     n = 0
     for case in cases:
-        image, label = _read_case(case, label_key)
+        if not isinstance(case, (str, bytes)) and len(case) == 3:
+            image, label, spacing = case
+        else:
+            (image, label), spacing = _read_case(case, label_key), voxelspacing
         if preproc_fn is not None:
             image = preproc_fn(image)
         pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
@@ -193,7 +203,8 @@ def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), st
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
         if nms:
             pred = components.largest_component_per_class(pred, num_classes)
-        m = calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface)
+        m = calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface, voxelspacing=spacing,
+                                      connectivity=connectivity)
         if metric_detail:
             for c, row in enumerate(m, 1):
                 print("%02d, class %d,\t%.5f, %.5f, %.5f, %.5f" % ((n, c) + tuple(row)))

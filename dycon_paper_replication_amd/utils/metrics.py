@@ -9,7 +9,8 @@ of the binary volumes plus two distance transforms per sample: more host time th
   * `AsyncTrainMetrics` takes it off the critical path: every `every`-th iteration the binary maps are copied to pinned memory
     asynchronously and a worker thread computes HD95 while the GPU trains on;
   * `compute_hd95_device` and `AsyncTrainMetrics(on_device=True)` are the opt-in device form (utils/surface.py, csrc/surface.hip):
-    exact surface distances for unit spacing, a device tensor back, no host copy, no worker.
+    exact surface distances, a device tensor back, no host copy, no worker; `compute_hd95_device` also takes medpy's
+    `voxelspacing` and `connectivity` (csrc/surface_spacing.hip).
 
 Those names are 2-class and refuse another width.  For 2..8 classes, under names of their own: `class_dice_from_logits` (per sample
 and foreground class, from one confusion count over the logits, csrc/evalc.hip), `AsyncClassTrainMetrics`, the device path of
@@ -194,13 +195,14 @@ def compute_hd95(pred, target, max_dist):
     return scores
 
 
-def compute_hd95_device(pred, target, max_dist):
-    """`compute_hd95` on the device (utils/surface.py; unit voxel spacing): pred / target are (B, X, Y, Z) binary volumes, numpy or
-    CUDA; returns a (B,) float64 device tensor.  A sample where either mask is empty gets max_dist (utils/metrics.py:117-118),
-    selected on the device: no host copy and no sync."""
+def compute_hd95_device(pred, target, max_dist, voxelspacing=None, connectivity=1):
+    """`compute_hd95` on the device (utils/surface.py): pred / target are (B, X, Y, Z) binary volumes, numpy or CUDA; returns a (B,)
+    float64 device tensor.  A sample where either mask is empty gets max_dist (utils/metrics.py:117-118), selected on the device: no
+    host copy and no sync.  voxelspacing / connectivity are medpy's (`surface.surface_metrics`); the defaults are unit spacing and
+    6-neighbour borders, as the reference calls hd95."""
     if len(pred.shape) != 4:
         raise ValueError(f"compute_hd95_device takes (B, X, Y, Z) volumes, got {tuple(pred.shape)}")
-    hd = surface.surface_metrics(pred, target)[:, 0]
+    hd = surface.surface_metrics(pred, target, voxelspacing=voxelspacing, connectivity=connectivity)[:, 0]
     return torch.where(torch.isnan(hd), torch.full_like(hd, float(max_dist)), hd)     # NaN = an empty border = an empty mask
 
 

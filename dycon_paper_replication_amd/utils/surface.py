@@ -1,9 +1,11 @@
-"""Surface distances on the device for unit voxel spacing (csrc/surface.hip): the squared-distance histograms between the borders of
-binary pairs, and HD95 / ASD (medpy.metric.binary.hd95 / asd, restated in `test_3d_patch._surface_distances`) read off them.
+"""Surface distances on the device: HD95 / ASD (medpy.metric.binary.hd95 / asd, restated in `test_3d_patch._surface_distances`) between
+the borders of binary pairs, with medpy's `voxelspacing` and `connectivity`.
 
-    surface_hists(a, b, classes=None)            -> (hist (S, 2, nbins) int32, nborder (S, 2) int32) device tensors
-    surface_metrics(a, b, classes=None, q=95.0)  -> (S, 5) float64 device tensor, no host sync
+    surface_hists(a, b, classes=None)            -> (hist (S, 2, nbins) int32, nborder (S, 2) int32) device tensors; unit spacing only
+    surface_metrics(a, b, classes=None, q=95.0, voxelspacing=None, connectivity=1)
+                                                 -> (S, 5) float64 device tensor, no host sync
     metrics_from_hists(hist, nborder, q=95.0)    -> the same (S, 5) in numpy fp64, usable without a GPU
+    metrics_from_distances(d_ab, d_ba, q=95.0)   -> one such row from the two directions' distances, numpy fp64, no GPU
 
 `a` (prediction) and `b` (ground truth) are numpy arrays or CUDA tensors of one shape, (X, Y, Z) or (n_vol, X, Y, Z), every axis at
 most 512.  With `classes=None` a voxel belongs to its mask when it is non-zero and there is one pair per volume.  With
@@ -12,10 +14,17 @@ of a case share one set of launches.  A row of the result is (percentile q of bo
 |border(a)|, |border(b)|); the first three are NaN when either border is empty.  hist[s, 0, d] counts the border voxels of a whose
 squared distance to the border of b is d, hist[s, 1] the other direction.
 
-Everything up to the final square root is integer arithmetic, so the histograms are exact and the same on every run.  Voxel spacing
-other than 1 is not covered: that stays on the host path.
+Two paths.  `voxelspacing=None` with `connectivity=1` is the histogram path (csrc/surface.hip): everything up to the final square
+root is integer arithmetic, so the histograms are exact and the same on every run.  Anything else -- a spacing, `(1, 1, 1)` given
+explicitly included, or connectivity 2 or 3 (18 or 26 neighbours in the erosion that defines the border) -- is the weighted path
+(csrc/surface_spacing.hip): an fp64 transform whose value is the exact minimum of the cost
+fl(fl(fl(wz dz^2) + fl(wy dy^2)) + fl(wx dx^2)), w = spacing^2, a radix select for the percentile and fixed-order sums for the means;
+also the same bits on every run.  `voxelspacing` is None, one positive number for all axes, or one per axis (X, Y, Z), as medpy
+normalises it; one spacing serves every volume of a call.  Not covered: 2-D inputs, a spacing per volume within one call.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -23,6 +32,7 @@ import torch
 from .. import _lib
 
 MAX_AXIS = 512
+MIN_SPACING, MAX_SPACING = 1e-150, 1e150      # the squares stay normal fp64 numbers
 WORKSPACE_BUDGET = 1 << 30        # bytes of distance-transform workspace per launch sequence; more pairs go in chunks
 
 
@@ -55,9 +65,8 @@ def _class_range(classes):
     return lo, n
 
 
-def surface_hists(a, b, classes=None):
-    """(hist (S, 2, nbins), nborder (S, 2)) as int32 device tensors (the kernels' unsigned counts; none reaches 2^31).  No host sync."""
-    lo, n_cls = _class_range(classes)
+def _kernel_inputs(a, b, lo):
+    """the prediction as uint8 and the ground truth as uint8 or int64, contiguous, on one device"""
     ta, tb = _operands(a, b)
     if lo == 0:                                   # membership is voxel != 0
         ta = ta if ta.dtype == torch.uint8 else ta.ne(0).to(torch.uint8)
@@ -66,7 +75,14 @@ def surface_hists(a, b, classes=None):
         if ta.dtype != torch.uint8:
             ta = torch.where((ta < 0) | (ta > 255), 0, ta).to(torch.uint8)
         tb = tb if tb.dtype in (torch.uint8, torch.int64) else tb.to(torch.int64)
-    ta, tb = ta.contiguous(), tb.contiguous()
+    return ta.contiguous(), tb.contiguous()
+
+
+def surface_hists(a, b, classes=None):
+    """(hist (S, 2, nbins), nborder (S, 2)) as int32 device tensors (the kernels' unsigned counts; none reaches 2^31).  No host sync.
+    Unit voxel spacing and 6-neighbour borders only."""
+    lo, n_cls = _class_range(classes)
+    ta, tb = _kernel_inputs(a, b, lo)
     n_vol, X, Y, Z = ta.shape
     nbins = nbins_of((X, Y, Z))
     hist = torch.empty((n_vol * n_cls, 2, nbins), dtype=torch.int32, device=ta.device)
@@ -89,13 +105,77 @@ def _metrics_of(hist, nborder, q):
     return out
 
 
-def surface_metrics(a, b, classes=None, q=95.0):
+def normalise_spacing(voxelspacing, connectivity=1):
+    """medpy's normalisation of `voxelspacing` for a 3-D volume: None -> None, a number -> that number for the three axes, a sequence
+    -> its three numbers; each finite and > 0.  connectivity must be 1, 2 or 3.  Returns (None or a 3-tuple of floats, connectivity).
+    Raises ValueError before anything touches the GPU."""
+    if isinstance(connectivity, bool) or connectivity not in (1, 2, 3):
+        raise ValueError(f"connectivity must be 1, 2 or 3 (6, 18 or 26 neighbours), got {connectivity!r}")
+    if voxelspacing is None:
+        return None, int(connectivity)
+    sp = np.asarray(voxelspacing, dtype=np.float64)
+    if sp.ndim == 0:
+        sp = np.repeat(sp, 3)
+    if sp.shape != (3,):
+        raise ValueError(f"voxelspacing takes one number or one per axis (X, Y, Z), got {voxelspacing!r}")
+    if not (np.isfinite(sp).all() and (sp > 0).all() and (sp >= MIN_SPACING).all() and (sp <= MAX_SPACING).all()):
+        raise ValueError(f"every voxel spacing must be finite, > 0 and within {MIN_SPACING:g}..{MAX_SPACING:g}, got {voxelspacing!r}")
+    return tuple(float(v) for v in sp), int(connectivity)
+
+
+def _spaced_metrics(a, b, classes, q, spacing, connectivity):
+    lo, n_cls = _class_range(classes)
+    ta, tb = _kernel_inputs(a, b, lo)
+    n_vol, X, Y, Z = ta.shape
+    out = torch.empty((n_vol * n_cls, 5), dtype=torch.float64, device=ta.device)
+    per_vol = int(_lib.query("dycon_surface_spaced_workspace", n_cls, X, Y, Z))
+    step = max(1, min(n_vol, WORKSPACE_BUDGET // per_vol, 32767 // n_cls))
+    ws = torch.empty(step * per_vol // 8, dtype=torch.float64, device=ta.device)
+    sp = (ctypes.c_double * 3)(*spacing)
+    stream = torch.cuda.current_stream(ta.device).cuda_stream
+    for v0 in range(0, n_vol, step):
+        nv = min(step, n_vol - v0)
+        _lib.call("dycon_surface_spaced_metrics", ta[v0:].data_ptr(), 1, tb[v0:].data_ptr(), tb.element_size(), nv, lo, n_cls, X, Y, Z,
+                  sp, connectivity, float(q), out[v0 * n_cls:].data_ptr(), ws.data_ptr(), ws.numel() * 8, stream)
+    return out
+
+
+def surface_metrics(a, b, classes=None, q=95.0, voxelspacing=None, connectivity=1):
     """(S, 5) float64 device tensor: percentile q of both directions, mean a -> b, mean b -> a, |border(a)|, |border(b)|.  No host
-    sync."""
+    sync.  voxelspacing=None with connectivity=1 is the histogram path; anything else the weighted path (module docstring)."""
     if not 0.0 <= float(q) <= 100.0:
         raise ValueError(f"percentile {q} outside [0, 100]")
-    hist, nborder = surface_hists(a, b, classes)
-    return _metrics_of(hist, nborder, q)
+    spacing, connectivity = normalise_spacing(voxelspacing, connectivity)
+    if spacing is None and connectivity == 1:
+        hist, nborder = surface_hists(a, b, classes)
+        return _metrics_of(hist, nborder, q)
+    return _spaced_metrics(a, b, classes, q, spacing or (1.0, 1.0, 1.0), connectivity)
+
+
+def metrics_from_distances(d_ab, d_ba, q=95.0):
+    """The finalise step of the weighted path in numpy fp64: the distances of the border voxels of a to the border of b and of b to a
+    -> (5,) = percentile q of their union (np.percentile's default rule, evaluated from the two order statistics as the kernel
+    does), mean a -> b, mean b -> a, the two counts; the first three NaN when either is empty.  The kernel adds the means in a fixed
+    order of its own: the two agree to rounding."""
+    d_ab, d_ba = np.asarray(d_ab, np.float64).ravel(), np.asarray(d_ba, np.float64).ravel()
+    na, nb = d_ab.size, d_ba.size
+    out = np.array([np.nan, np.nan, np.nan, na, nb])
+    if na == 0 or nb == 0:
+        return out
+    n = na + nb
+    vi = (n - 1) * (float(q) / 100.0)
+    gamma = vi - np.floor(vi)
+    lo, hi = int(np.floor(vi)), int(np.floor(vi)) + 1
+    if vi >= n - 1:
+        lo = hi = n - 1
+    if vi < 0:
+        lo = hi = 0
+    both = np.partition(np.hstack((d_ab, d_ba)), (lo, hi))
+    v0, v1 = both[lo], both[hi]
+    diff = v1 - v0
+    out[0] = v1 - diff * (1.0 - gamma) if gamma >= 0.5 else v0 + diff * gamma
+    out[1], out[2] = d_ab.sum() / na, d_ba.sum() / nb
+    return out
 
 
 def metrics_from_hists(hist, nborder, q=95.0):

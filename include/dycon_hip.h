@@ -628,6 +628,22 @@ int dycon_surface_hist(const void* a, int a_bytes, const void* b, int b_bytes, i
 int dycon_surface_metrics(const unsigned int* hist, const unsigned int* nborder, int S, int nbins, double q, double* out,
                           dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- surface distances, any voxel spacing (csrc/surface_spacing.hip)
+ * medpy's hd95 / asd with their voxelspacing and connectivity arguments.  a, b, n_vol, cls_lo, n_cls, X, Y, Z and the pair order are
+ * those of dycon_surface_hist.  spacing: 3 host doubles for the axes X, Y, Z, read during the call, each finite, > 0 and within
+ * 1e-150..1e150 (the squares stay normal numbers).  connectivity 1, 2, 3: border = m ^ erode(m) with 6, 18 or 26 neighbours, the
+ * outside of the volume as background.  Per pair and mask the fp64 transform of the border set with the cost of an offset
+ * (dx, dy, dz) = fl(fl(fl(wz dz^2) + fl(wy dy^2)) + fl(wx dx^2)), w = spacing^2, no contraction: the exact minimum of that cost,
+ * whatever the grid.  out (S, 5) double as dycon_surface_metrics writes it: percentile q of both directions by a radix select over
+ * the costs' bit patterns (np.percentile's default linear rule on their square roots), mean a->b and mean b->a as fp64 sums in an
+ * order fixed by the shape, |border(a)|, |border(b)|; the first three are NaN when either border is empty.  Integer atomics only: the
+ * same bits on every run.  No allocation, no host synchronisation.  workspace: dycon_surface_spaced_workspace bytes, 8-byte aligned
+ * (2 fp64 volumes per pair and a fixed block of select state). */
+size_t dycon_surface_spaced_workspace(int S, int X, int Y, int Z);
+int dycon_surface_spaced_metrics(const void* a, int a_bytes, const void* b, int b_bytes, int n_vol, int cls_lo, int n_cls, int X, int Y,
+                                 int Z, const double* spacing, int connectivity, double q, double* out, void* workspace,
+                                 size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- 3-D connected components (csrc/components.hip)
  * The `nms` step of code/utils/test_3d_patch.py:19-26 (skimage.measure.label + the largest component) without a host copy.  vol:
  * (n_vol, X, Y, Z) uint8 or int64 (vol_bytes 1 or 8), Z innermost, every axis in 1..512, at most 65535 volumes and 2^31 - 1 voxels per
