@@ -64,12 +64,13 @@ def _connectivity(connectivity):
     return c
 
 
-def _pieces(t):
-    """(first volume, volume count) of the launch sequences of one call, with the workspace they share"""
+def _pieces(t, workspace="dycon_cc_workspace", root_maps=1):
+    """(first volume, volume count) of the launch sequences of one call, with the workspace they share: `workspace` names the size
+    query, `root_maps` int32 root maps are held next to it"""
     n_vol, X, Y, Z = t.shape
-    per_vol = int(_lib.query("dycon_cc_workspace", 1, X, Y, Z)) + 4 * X * Y * Z
+    per_vol = int(_lib.query(workspace, 1, X, Y, Z)) + 4 * root_maps * X * Y * Z
     step = max(1, min(n_vol, WORKSPACE_BUDGET // per_vol, MAX_VOXELS // (X * Y * Z), 65535))
-    ws = torch.empty(int(_lib.query("dycon_cc_workspace", step, X, Y, Z)), dtype=torch.uint8, device=t.device)
+    ws = torch.empty(int(_lib.query(workspace, step, X, Y, Z)), dtype=torch.uint8, device=t.device)
     return [(v0, min(step, n_vol - v0)) for v0 in range(0, n_vol, step)], ws
 
 

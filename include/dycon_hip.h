@@ -667,6 +667,27 @@ int dycon_cc_labels(const int* root, int n_vol, int X, int Y, int Z, int* labels
 int dycon_cc_largest(const void* vol, int vol_bytes, const int* root, int n_vol, int X, int Y, int Z, int n_cls, uint8_t* out,
                      int* win_size, int* win_root, void* workspace, size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- lesion-wise statistics (csrc/lesions.hip)
+ * From the root maps of a prediction and a ground truth to per-lesion sizes and overlaps and the per-volume detection counts behind
+ * lesion-wise F1, lesion-count difference and volume difference.  root_pred, root_gt: (n_vol, X, Y, Z) int32 as dycon_cc_roots
+ * writes them with by_value == 0 (0 = background, else 1 + the smallest linear index of the voxel's component inside its volume;
+ * a value outside 1..X*Y*Z is read as background); shape limits are those of dycon_cc_roots.
+ *   workspace: four sections of dycon_lesion_workspace / 4 bytes, each (n_vol, X*Y*Z) int32 addressed by root - 1 inside the volume:
+ *            size of the prediction's lesions | their overlap | size of the ground truth's lesions | their overlap.  size = the voxel
+ *            count of the component; overlap = the number of its voxels that are foreground in the other mask after the size filter
+ *            (0 for a lesion the filter removes).  Entries that are no root are 0.
+ *   filter : min_voxels >= 1.  A component of fewer voxels is removed from its own mask before anything else is counted, on both
+ *            sides: a removed predicted lesion is no false positive and lends no overlap, a removed ground-truth lesion is no
+ *            false negative.  Whole components go, so the survivors keep their roots.
+ *   counts : (n_vol, 8) int64 over the surviving lesions: n_gt, n_pred (components), tp (ground-truth components with overlap > 0),
+ *            fn (n_gt - tp), fp (predicted components with overlap == 0), vox_gt, vox_pred, vox_and (voxels of the two masks and
+ *            of their intersection).  Overlap means shared voxels: lesions that only touch do not overlap, whatever the connectivity.
+ * Integer atomics only, aggregated per wave (sizes, overlaps) and per workgroup (counts): the same bits on every run.  Two
+ * hipMemsetAsync and three launches; no allocation, no host synchronisation, no workgroup waits on another. */
+size_t dycon_lesion_workspace(int n_vol, int X, int Y, int Z);
+int dycon_lesion_counts(const int* root_pred, const int* root_gt, int n_vol, int X, int Y, int Z, int min_voxels, long long* counts,
+                        void* workspace, size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
  * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
  * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
