@@ -152,6 +152,8 @@ SIGNATURES = {
     "dycon_cc_largest": (I, [P, I, P, I, I, I, I, I, P, P, P, P, Z, P]),
     "dycon_lesion_workspace": (Z, [I, I, I, I]),
     "dycon_lesion_counts": (I, [P, P, I, I, I, I, I, P, P, Z, P]),
+    "dycon_sdf_workspace": (Z, [I, I, I, I]),
+    "dycon_sdf": (I, [P, I, I, I, I, I, I, I, I, I, I, P, P, Z, P]),
     "dycon_simhist_workspace": (Z, [I, I, I, I]),
     "dycon_simhist": (I, [P, P, I, I, I, I, F, I, P, P, P, P, Z, P]),
     "dycon_tap_gather": (I, [P, P, I, I, I, I, I, I, P, I, P]),

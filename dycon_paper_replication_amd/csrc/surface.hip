@@ -11,9 +11,8 @@
 //   y, x pass   out[l] = min_l' g[l'] + (l - l')^2 from a (line x 64 z) tile in LDS, the search pruned at (l - l')^2 >= best
 //   histogram   a border voxel is a voxel whose own transform is 0
 #include "common.h"
+#include "surface_edt.h"
 
-#define SURFACE_FAR (1 << 29)                     // + 2 * 511^2 stays below 2^31
-#define SURFACE_MAX_AXIS 512
 #define SURFACE_TILE_BINS 256
 #define SURFACE_LDS_BINS 2048                     // squared distances below 45^2 are counted in LDS first
 #define SURFACE_MAX_TILES 3072                    // 3 * 511^2 + 1 bins in tiles of 256
@@ -81,37 +80,6 @@ __global__ __launch_bounds__(256) void surface_border_z_kernel(const T* __restri
             }
             if (z < Z) out[z] = best < NONE ? best * best : SURFACE_FAR;
         }
-    }
-}
-
-// In place along one of the two outer axes: blockIdx.z picks the volume of d2, blockIdx.y the index along the other outer axis,
-// blockIdx.x the 64-wide z tile.  The whole (L x 64) tile is in LDS before anything is written back.
-template <int LMAX>
-__global__ __launch_bounds__(256) void surface_axis_pass_kernel(int* __restrict__ d2, long long V, int L, long long line_stride,
-                                                                long long other_stride, int Z) {
-    __shared__ int tile[LMAX][64];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int z = blockIdx.x * 64 + lane;
-    const bool live = z < Z;
-    int* __restrict__ base = d2 + (long long)blockIdx.z * V + (long long)blockIdx.y * other_stride + z;
-    for (int l = w; l < L; l += 4) tile[l][lane] = live ? base[l * line_stride] : SURFACE_FAR;
-    __syncthreads();
-    if (!live) return;
-    for (int l = w; l < L; l += 4) {
-        int best = tile[l][lane];
-        const int reach = max(l, L - 1 - l);
-        // four distances per trip, so that eight independent LDS reads are in flight; a candidate past the pruning bound cannot win
-        for (int d = 1; d <= reach && d * d < best; d += 4) {
-            int cand = best;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = d + j, ee = e * e, lo = l - e, hi = l + e;
-                const int below = tile[max(lo, 0)][lane], above = tile[min(hi, L - 1)][lane];
-                cand = min(cand, min(lo >= 0 ? below + ee : SURFACE_FAR, hi < L ? above + ee : SURFACE_FAR));
-            }
-            best = cand;
-        }
-        base[l * line_stride] = best;
     }
 }
 
@@ -253,14 +221,6 @@ extern "C" size_t dycon_surface_workspace(int S, int X, int Y, int Z) {
     return (size_t)S * 2 * (size_t)X * Y * Z * sizeof(int);
 }
 
-static void surface_axis_pass(int* d2, long long V, int L, long long line_stride, int n_other, long long other_stride, int Z, int S,
-                              hipStream_t stream) {
-    dim3 grid(cdiv(Z, 64), n_other, 2 * S);
-    if (L <= 128) surface_axis_pass_kernel<128><<<grid, 256, 0, stream>>>(d2, V, L, line_stride, other_stride, Z);
-    else if (L <= 256) surface_axis_pass_kernel<256><<<grid, 256, 0, stream>>>(d2, V, L, line_stride, other_stride, Z);
-    else surface_axis_pass_kernel<SURFACE_MAX_AXIS><<<grid, 256, 0, stream>>>(d2, V, L, line_stride, other_stride, Z);
-}
-
 extern "C" int dycon_surface_hist(const void* a, int a_bytes, const void* b, int b_bytes, int n_vol, int cls_lo, int n_cls, int X, int Y,
                                   int Z, unsigned int* hist, unsigned int* nborder, void* workspace, size_t ws_bytes,
                                   dycon_stream_t stream) {
@@ -291,8 +251,8 @@ extern "C" int dycon_surface_hist(const void* a, int a_bytes, const void* b, int
         surface_border_z_kernel<unsigned char><<<rows, 256, 0, st>>>((const unsigned char*)b, n_cls, cls_lo, X, Y, Z, 1, d2);
     else
         surface_border_z_kernel<long long><<<rows, 256, 0, st>>>((const long long*)b, n_cls, cls_lo, X, Y, Z, 1, d2);
-    if (Y > 1) surface_axis_pass(d2, V, Y, Z, X, (long long)Y * Z, Z, (int)S, st);      // lines along y at fixed x
-    if (X > 1) surface_axis_pass(d2, V, X, (long long)Y * Z, Y, Z, Z, (int)S, st);      // lines along x at fixed y
+    if (Y > 1) surface_axis_pass(d2, V, Y, Z, X, (long long)Y * Z, Z, 2 * (int)S, st);  // lines along y at fixed x
+    if (X > 1) surface_axis_pass(d2, V, X, (long long)Y * Z, Y, Z, Z, 2 * (int)S, st);  // lines along x at fixed y
     const long long blocks = (V + 256 * 16 - 1) / (256 * 16);                              // 16 voxels per thread, 256 workgroups at most
     surface_hist_kernel<<<dim3((int)(blocks > 256 ? 256 : blocks), (int)S), 256, 0, st>>>(d2, V, nbins, nborder, hist);
     DYCON_LAUNCH_CHECK();

@@ -15,3 +15,4 @@ from . import components  # noqa: E402,F401
 from . import device_eval  # noqa: E402,F401
 from . import lesions  # noqa: E402,F401
 from . import isles_eval  # noqa: E402,F401
+from . import util  # noqa: E402,F401

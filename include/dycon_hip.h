@@ -688,6 +688,26 @@ size_t dycon_lesion_workspace(int n_vol, int X, int Y, int Z);
 int dycon_lesion_counts(const int* root_pred, const int* root_gt, int n_vol, int X, int Y, int Z, int min_voxels, long long* counts,
                         void* workspace, size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- signed distance maps (csrc/sdf.hip)
+ * compute_sdf of code/utils/util.py:205-236 for S = n_vol * n_cls maps in one set of launches.  labels: (n_vol, X, Y, Z) uint8 or
+ * int64 (label_bytes 1 or 8), Z innermost, every axis in 1..512.  Map s = v * n_cls + k takes volume v; its foreground is voxel != 0
+ * when cls_lo == 0 (n_cls must be 1: the reference's astype(bool)), voxel == cls_lo + k otherwise (cls_lo + n_cls <= 256).
+ * out: (S, n_rep, X, Y, Z) of out_bytes 4 (fp32) or 8 (fp64); the n_rep copies of a map are the reference's broadcast into an
+ * output with a channel axis.  Per map, all in fp64 from exact int32 squared distances (util.py:219-232):
+ *   no foreground voxel              +0.0 everywhere
+ *   no background voxel              NaN everywhere (the reference's 0 / 0)
+ *   foreground, squared distance to the background == 1     +0.0: the inner boundary of connectivity 1, which the faces of the
+ *                                    volume do not create (not the border rule of dycon_surface_hist)
+ *   other foreground voxels          -(sqrt(d2 to the background) / sqrt(max of it over the foreground))
+ *   background voxels                +(sqrt(d2 to the foreground) / sqrt(max of it over the background))
+ * normalize == 0 leaves the two divisions out: the signed distance in voxels with the same zeroed boundary and the same NaN rule.
+ * An fp32 output is the fp64 value rounded once.  Unsigned integer atomicMax / atomicOr only: the same bits on every run.  One
+ * hipMemsetAsync and at most five launches on the stream; no allocation, no host synchronisation.  workspace: 2 int32 volumes and
+ * 4 unsigned words per map, 4-byte aligned. */
+size_t dycon_sdf_workspace(int S, int X, int Y, int Z);
+int dycon_sdf(const void* labels, int label_bytes, int n_vol, int cls_lo, int n_cls, int X, int Y, int Z, int normalize, int n_rep,
+              int out_bytes, void* out, void* workspace, size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- similarity monitor (utils/monitor.py:7-50)
  * The two histograms monitor_similarity_distributions draws, without the (B, N, N) similarity matrix: Gram tiles are recomputed
  * on MFMA in two sweeps (set ranges, then bins).  feat: (B, N, Dm) raw rows (dtype storage, Dm <= 256), normalised as F.normalize
