@@ -164,6 +164,8 @@ SIGNATURES = {
     "dycon_small_gemm": (I, [P, L, L, P, L, L, P, L, I, I, I, I, P]),
     "dycon_copy_segments": (I, [P, P, P, I, P]),
     "dycon_assemble_batch": (I, [P, P, P, I, I, I, I, P, P, I, P]),
+    "dycon_sw_gather": (I, [P, I, I, I, P, I, I, I, I, I, I, P, P]),
+    "dycon_sw_accumulate_ens": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, I, I, I, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

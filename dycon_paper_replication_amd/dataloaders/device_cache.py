@@ -1,7 +1,8 @@
 """Device-resident training data: the whole training set cached in HBM, batches assembled by one HIP launch.
 
     DeviceVolumeCache(samples, device, pre, max_bytes)        every case once: images fp32, labels uint8, two arenas in HBM
-    draw_plan(shapes, indices, patch_size, rot_flip, center)  host: the crops / rotations / flips RandomCrop + RandomRotFlip would draw
+    draw_plan(shapes, indices, patch_size, rot_flip, center, order)   host: the crops / rotations / flips RandomCrop + RandomRotFlip
+                                                              would draw, crop first (BraTS, Pancreas, ISLES) or rot/flip first (LA)
     apply_plan_host(plan, images, labels)                     host: numpy restatement of the kernel (the CPU-testable twin)
     assemble_batch(cache, plan, out, label_dtype)             device: dycon_assemble_batch, one launch per 16 samples
     DeviceBatchLoader(cache, batch_sampler, patch_size, ...)  iterates a batch sampler, yields {"image", "label"} device batches
@@ -128,19 +129,61 @@ def _pads(shape, patch):
     return (0, 0, 0)
 
 
-def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False):
+ORDERS = ("crop_rotflip", "rotflip_crop")
+
+
+def _rotflip_crop_record(shape, patch):
+    """One sample of the LA order, ``RandomRotFlip()`` then ``RandomCrop(patch)``: draws k, the axis, then the three crop offsets
+    with bounds from the ROTATED, then padded shape -> (origin in stored coordinates, k, axis).
+
+    A crop of a rotated and flipped array is the rotation and flip of a crop of the stored array at a mapped origin, and the
+    symmetric zero pad commutes with both, so the record is one the kernel already executes.  With r = flip(rot90(x, k), axis) of
+    shape (R0, R1, Z) and the crop at (u, v) of r (offset - pad), the flip turns the origin of its axis into R - u - P, and rot90
+    maps the pair (U, V) to stored (U, V) | (V, Y - U - P1) | (X - U - P0, Y - V - P1) | (X - V - P0, U) for k = 0 | 1 | 2 | 3."""
+    X, Y, Z = shape
+    k = np.random.randint(0, 4)
+    axis = np.random.randint(0, 2)
+    R = (Y, X, Z) if k & 1 else (X, Y, Z)
+    pad = _pads(R, patch)
+    w, h, d = (R[a] + 2 * pad[a] for a in range(3))
+    w1 = np.random.randint(0, w - patch[0])
+    h1 = np.random.randint(0, h - patch[1])
+    d1 = np.random.randint(0, d - patch[2])
+    u, v = w1 - pad[0], h1 - pad[1]
+    U = R[0] - u - patch[0] if axis == 0 else u
+    V = R[1] - v - patch[1] if axis == 1 else v
+    ox, oy = ((U, V), (V, Y - U - patch[1]), (X - U - patch[0], Y - V - patch[1]), (X - V - patch[0], U))[k]
+    return (ox, oy, d1 - pad[2]), k, axis
+
+
+def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False, order="crop_rotflip"):
     """The plan of one batch: a PLAN_DTYPE record per entry of `indices` (case numbers into `shapes`).
 
     Pure host code.  Consumes ``np.random`` exactly as ``RandomCrop(patch_size)`` followed by ``RandomRotFlip()`` do for each index
     in order: three randint for the crop, bounds from the PADDED shape, then k, then the axis (rot_flip=False: the crop only,
     k = 0, no flip).  center=True gives the CenterCrop origin and draws nothing.  An odd k with patch_size[0] != patch_size[1]
-    raises ValueError: the rotated crop would not have the patch's shape (the reference could not stack such a batch either)."""
+    raises ValueError: the rotated crop would not have the patch's shape (the reference could not stack such a batch either).
+
+    order="rotflip_crop" is the LA pipelines' ``RandomRotFlip()`` BEFORE ``RandomCrop(patch_size)``: k, the axis, then the three
+    crop offsets from the rotated, then padded shape, translated into the same records (`_rotflip_crop_record`).  It needs
+    rot_flip=True and center=False (without the rotation, or with a drawn-nothing centre crop, there is one order only); an odd k
+    still needs a square patch, because the kernel rotates the crop."""
     patch = tuple(int(v) for v in patch_size)
     if len(patch) != 3 or min(patch) <= 0:
         raise ValueError(f"patch_size must be three positive sizes, got {patch_size}")
+    if order not in ORDERS:
+        raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
+    if order == "rotflip_crop" and (center or not rot_flip):
+        raise ValueError("order='rotflip_crop' is the order of RandomRotFlip and RandomCrop: it needs rot_flip=True and center=False")
     plan = np.zeros(len(indices), dtype=PLAN_DTYPE)
     for n, idx in enumerate(indices):
         shape = shapes[idx]
+        if order == "rotflip_crop":
+            origin, k, axis = _rotflip_crop_record(shape, patch)
+            if (k & 1) and patch[0] != patch[1]:
+                raise ValueError(f"rot90 by k = {k} of a {patch[0]} x {patch[1]} crop does not give a {patch[0]} x {patch[1]} patch")
+            plan[n] = (idx, origin, k, axis, patch)
+            continue
         pad = _pads(shape, patch)
         w, h, d = (shape[a] + 2 * pad[a] for a in range(3))
         k, axis = 0, -1
@@ -241,10 +284,16 @@ class DeviceBatchLoader:
     For a seeded ``np.random`` the batches equal those of ``DataLoader(dataset, batch_sampler=batch_sampler, num_workers=0)`` with
     ``transform = Compose([RandomCrop(patch_size), RandomRotFlip(), ToTensor()])`` bit for bit (label_dtype=torch.int64 for
     ToTensor's dtype; `pre=SagittalToAxial()` on the cache for the BraTS chain; rot_flip=False leaves RandomRotFlip out).  The
-    reference's multi-worker stream is not reproducible by anything."""
+    reference's multi-worker stream is not reproducible by anything.  order="rotflip_crop": the LA chain
+    ``Compose([RandomRotFlip(), RandomCrop(patch_size), ToTensor()])`` (dataloaders/la_heart.py) instead, see `draw_plan`."""
 
-    def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8):
+    def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8, order="crop_rotflip"):
+        if order not in ORDERS:
+            raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
+        if order == "rotflip_crop" and not rot_flip:
+            raise ValueError("order='rotflip_crop' needs rot_flip=True")
         self.cache, self.batch_sampler, self.rot_flip, self.label_dtype = cache, batch_sampler, rot_flip, label_dtype
+        self.order = order
         self.patch_size = tuple(int(v) for v in patch_size)
         self._ring, self._n = [None, None], 0
 
@@ -255,7 +304,7 @@ class DeviceBatchLoader:
         """the host side of an epoch on its own: the plan of every batch, in order (draws as iterating the loader does)"""
         shapes = self.cache.shapes
         for batch in self.batch_sampler:
-            yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip)
+            yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
 
     def __iter__(self):
         for plan in self.plans():

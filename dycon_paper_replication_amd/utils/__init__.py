@@ -16,3 +16,11 @@ from . import device_eval  # noqa: E402,F401
 from . import lesions  # noqa: E402,F401
 from . import isles_eval  # noqa: E402,F401
 from . import util  # noqa: E402,F401
+
+# the reference's two-model (`_plus`) evaluators, its LA validation loops and two small helpers (code/utils/test_3d_patch.py:14-17,
+# :28-49, :354-476, :488-494) live in utils/ensemble_eval.py; test_3d_patch.py had none of them, so binding them there rebinds nothing
+from . import ensemble_eval  # noqa: E402,F401
+
+for _name in ensemble_eval.REFERENCE_NAMES:
+    setattr(test_3d_patch, _name, getattr(ensemble_eval, _name))
+del _name

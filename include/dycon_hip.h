@@ -777,6 +777,25 @@ typedef struct {
 int dycon_assemble_batch(const float* images, const uint8_t* labels, const dycon_crop_job_t* jobs_host, int njobs, int P0, int P1,
                          int P2, float* out_image, void* out_label, int label_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- model-ensemble sliding window (csrc/ensemble.hip;
+ * code/utils/test_3d_patch.py:415-476, test_single_case_plus)
+ * dycon_sw_gather: out (n, 1, p0, p1, p2) fp32 = windows [first, first + n) of a case, n in 1..64, in one launch.  vol: the UNPADDED
+ * (w, h, d) fp32 volume; origins_dev: n_origins x 3 ints on the device, the window corners of the whole case in the coordinates of
+ * the centre-padded volume (:418-439, :449-455: an axis shorter than the window is padded to it, (p - size) / 2 voxels in front).
+ * The pad is index arithmetic: a source index outside the stored volume reads as 0, so out equals slicing the zero-padded volume bit
+ * for bit and no origin can make the kernel read outside vol.  Rejected before any launch: a null pointer, a non-positive axis, n
+ * outside 1..64, [first, first + n) outside the table. */
+int dycon_sw_gather(const float* vol, int w, int h, int d, const int* origins_dev, int n_origins, int first, int n, int p0, int p1,
+                    int p2, float* out, dycon_stream_t stream);
+/* dycon_sw_accumulate for M = 2..4 models with C = 2..8 classes (:459-470): logits0..logits{M-1} are fp32 (n_patches, p0, p1, p2, C),
+ * the rest is ignored (pass NULL).  Per covered voxel and class the logits are summed in model order, ((l0 + l1) + l2) + l3, and
+ * divided by M ((y1_l + y1_r) / 2, :462); class 1 of the softmax of the mean is added to score and 1 to cnt, with the expressions of
+ * dycon_sw_accumulate (C == 2) and dycon_sw_accumulate_c (C > 2): the same model twice gives their bits ((a + a) / 2 == a).
+ * origins_dev: the n_patches x 3 corners of THIS chunk.  Voxel-centric, fixed window order, no atomics: deterministic. */
+int dycon_sw_accumulate_ens(const float* logits0, const float* logits1, const float* logits2, const float* logits3, int M, int C,
+                            int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score, float* cnt, int D0, int D1,
+                            int D2, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
