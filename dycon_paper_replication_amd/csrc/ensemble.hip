@@ -6,13 +6,12 @@
 //     table of window origins that was uploaded once per case.  The centre pad of a volume smaller than the window (:418-439) is
 //     index arithmetic: the origins are in padded coordinates, a source index outside the stored volume reads as 0 (the convention
 //     of csrc/datapath.hip).  A pure copy: bit for bit the slices of the zero-padded volume.
-//   - sw_accumulate_ens_kernel is the voxel-centric accumulate of csrc/eval.hip (fixed window order, no atomics) over M = 2..4
-//     models: per covered voxel and class the logits are summed in model order in fp32, divided by M, and class 1 of the softmax is
-//     scored with the expressions of sw_accumulate_kernel (C == 2) and sw_accumulate_c_kernel (C > 2).  (a + a) / 2 == a in fp32, so
-//     an ensemble of a model with itself gives the single-model kernels' bits.
-// Both are bandwidth-bound passes with coalesced access along the last axis and nothing else was tuned.  dycon_sw_finalize (eval.hip)
-// turns the maps into the label and the probability.
-#include "common.h"
+//   - sw_accumulate_kernel<M, false> (sw_accumulate.h), M = 2..4, is the accumulate of the single-model evaluator reading the mean
+//     of the models' logits: per covered voxel and class they are summed in model order in fp32 and divided by M, and class 1 of the
+//     softmax is scored as dycon_sw_accumulate does for C == 2 and dycon_sw_accumulate_c for C > 2.
+// The gather is a bandwidth-bound pass with coalesced access along the last axis and nothing else was tuned.  dycon_sw_finalize
+// (eval.hip) turns the maps into the label and the probability.
+#include "sw_accumulate.h"
 
 // blockIdx.y = window of the chunk; blockIdx.x strides over its p0 * p1 rows x G groups of 4 elements of the last axis
 __global__ __launch_bounds__(256) void sw_gather_kernel(const float* __restrict__ vol, int w, int h, int d, int lo0, int lo1, int lo2,
@@ -72,74 +71,16 @@ extern "C" int dycon_sw_gather(const float* vol, int w, int h, int d, const int*
     return DYCON_OK;
 }
 
-struct EnsLogits {
-    const float* l[4];
-};
-
-// mean over the models of logit k of one voxel of one window: ((l0 + l1) + l2) + l3, then / M
-template <int M> __device__ __forceinline__ float ens_mean(const EnsLogits& in, long long at) {
-    float x = in.l[0][at] + in.l[1][at];
-    if constexpr (M > 2) x += in.l[2][at];
-    if constexpr (M > 3) x += in.l[3][at];
-    return x / (float)M;
-}
-
-template <int M>
-__global__ __launch_bounds__(256) void sw_accumulate_ens_kernel(EnsLogits in, int C, int nb, int p0, int p1, int p2,
-                                                                const int* __restrict__ origins, float* __restrict__ score,
-                                                                float* __restrict__ cnt, int D0, int D1, int D2) {
-    __shared__ int org[3 * 64];
-    for (int i = threadIdx.x; i < 3 * nb; i += 256) org[i] = origins[i];
-    __syncthreads();
-    const long long total = (long long)D0 * D1 * D2;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % D2);
-        const long long q = i / D2;
-        const int b_ = (int)(q % D1), a = (int)(q / D1);
-        float s = 0.f, n = 0.f;
-        for (int p = 0; p < nb; ++p) {
-            const int la = a - org[3 * p], lb = b_ - org[3 * p + 1], lc = c - org[3 * p + 2];
-            if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
-                const long long at = ((((long long)p * p0 + la) * p1 + lb) * p2 + lc) * C;
-                if (C == 2) {
-                    const float x0 = ens_mean<M>(in, at), x1 = ens_mean<M>(in, at + 1);
-                    s += 1.f / (1.f + __expf(x0 - x1));      // softmax(mean logits)[1]: the expression of sw_accumulate_kernel
-                } else {
-                    float x[8], m = -INFINITY, z = 0.f;       // the max-shifted form of sw_accumulate_c_kernel
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (k < C) { x[k] = ens_mean<M>(in, at + k); m = fmaxf(m, x[k]); }
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (k < C) { x[k] = expf(x[k] - m); z += x[k]; }
-                    s += x[1] / z;
-                }
-                n += 1.f;
-            }
-        }
-        if (n > 0.f) { score[i] += s; cnt[i] += n; }
-    }
-}
-
 extern "C" int dycon_sw_accumulate_ens(const float* logits0, const float* logits1, const float* logits2, const float* logits3, int M,
                                        int C, int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score, float* cnt,
                                        int D0, int D1, int D2, dycon_stream_t stream) {
     DYCON_REQUIRE(M >= 2 && M <= 4, "sw_accumulate_ens: M = %d models (2..4)", M);
     DYCON_REQUIRE(C >= 2 && C <= 8, "sw_accumulate_ens: C = %d (2..8: class 1 is scored)", C);
-    EnsLogits in = {{logits0, logits1, logits2, logits3}};
+    SwLogits in = {{logits0, logits1, logits2, logits3}};
     for (int m = 0; m < M; ++m) DYCON_REQUIRE(in.l[m], "sw_accumulate_ens: logits of model %d are null (M = %d)", m, M);
     for (int m = M; m < 4; ++m) in.l[m] = nullptr;
     DYCON_REQUIRE(origins_dev && score && cnt, "sw_accumulate_ens: null pointer");
-    DYCON_REQUIRE(n_patches > 0 && n_patches <= 64 && p0 > 0 && p1 > 0 && p2 > 0 && D0 >= p0 && D1 >= p1 && D2 >= p2,
-                  "sw_accumulate_ens: bad shape (%d patches of %dx%dx%d in %dx%dx%d)", n_patches, p0, p1, p2, D0, D1, D2);
-    long long blocks = ((long long)D0 * D1 * D2 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (M == 2)
-        sw_accumulate_ens_kernel<2><<<(int)blocks, 256, 0, stream>>>(in, C, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2);
-    else if (M == 3)
-        sw_accumulate_ens_kernel<3><<<(int)blocks, 256, 0, stream>>>(in, C, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2);
-    else
-        sw_accumulate_ens_kernel<4><<<(int)blocks, 256, 0, stream>>>(in, C, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2);
-    DYCON_LAUNCH_CHECK();
-    return DYCON_OK;
+    if (int e = sw_check_shape("sw_accumulate_ens", n_patches, p0, p1, p2, D0, D1, D2)) return e;
+    const auto launch = M == 2 ? sw_accumulate_launch<2, false> : M == 3 ? sw_accumulate_launch<3, false> : sw_accumulate_launch<4, false>;
+    return launch(in, C, C == 2, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, nullptr, nullptr, stream);
 }

@@ -1,34 +1,8 @@
 // Sliding-window evaluation on the device: code/utils/test_3d_patch.py:293-351 (test_single_case) and the
 // overlap counts behind medpy's dc / jc (code/utils/test_3d_patch.py:496-508, calculate_metric_percase).
 //
-// The reference copies every patch's softmax to the host and accumulates score / count maps with numpy slicing.  Here the maps
-// stay in HBM: after a batch of patches went through the network, one voxel-centric pass adds, for every volume voxel, the class-1
-// probability of each patch of the batch that covers it (fixed patch order: deterministic, no atomics although windows overlap).
-#include "common.h"
-
-__global__ __launch_bounds__(256) void sw_accumulate_kernel(const float* __restrict__ logits, int nb, int p0, int p1, int p2,
-                                                            const int* __restrict__ origins, float* __restrict__ score,
-                                                            float* __restrict__ cnt, int D0, int D1, int D2) {
-    __shared__ int org[3 * 64];
-    for (int i = threadIdx.x; i < 3 * nb; i += 256) org[i] = origins[i];
-    __syncthreads();
-    const long long total = (long long)D0 * D1 * D2;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % D2);
-        const long long q = i / D2;
-        const int b_ = (int)(q % D1), a = (int)(q / D1);
-        float s = 0.f, n = 0.f;
-        for (int p = 0; p < nb; ++p) {
-            const int la = a - org[3 * p], lb = b_ - org[3 * p + 1], lc = c - org[3 * p + 2];
-            if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
-                const float2 l = *reinterpret_cast<const float2*>(logits + ((((long long)p * p0 + la) * p1 + lb) * p2 + lc) * 2);
-                s += 1.f / (1.f + __expf(l.x - l.y));        // softmax(logits)[1]   (test_3d_patch.py:334-337)
-                n += 1.f;
-            }
-        }
-        if (n > 0.f) { score[i] += s; cnt[i] += n; }
-    }
-}
+// The accumulate kernel of the sliding window lives in sw_accumulate.h; the entry points here are its one-model, class-1 forms.
+#include "sw_accumulate.h"
 
 __global__ __launch_bounds__(256) void sw_finalize_kernel(const float* __restrict__ score, const float* __restrict__ cnt, long long n,
                                                           float thresh, unsigned char* __restrict__ label, float* __restrict__ prob) {
@@ -97,58 +71,19 @@ extern "C" int dycon_batch_overlap(const float* logits, const void* gt, int gt_b
 extern "C" int dycon_sw_accumulate(const float* logits, int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score,
                                    float* cnt, int D0, int D1, int D2, dycon_stream_t stream) {
     DYCON_REQUIRE(logits && origins_dev && score && cnt, "sw_accumulate: null pointer");
-    DYCON_REQUIRE(n_patches > 0 && n_patches <= 64 && p0 > 0 && p1 > 0 && p2 > 0 && D0 >= p0 && D1 >= p1 && D2 >= p2,
-                  "sw_accumulate: bad shape (%d patches of %dx%dx%d in %dx%dx%d)", n_patches, p0, p1, p2, D0, D1, D2);
-    long long blocks = ((long long)D0 * D1 * D2 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    sw_accumulate_kernel<<<(int)blocks, 256, 0, stream>>>(logits, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2);
-    DYCON_LAUNCH_CHECK();
-    return DYCON_OK;
+    if (int e = sw_check_shape("sw_accumulate", n_patches, p0, p1, p2, D0, D1, D2)) return e;
+    return sw_accumulate_launch<1, false>({{logits}}, 2, 1, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, nullptr, nullptr,
+                                          stream);
 }
 
-// C-class models (C in 2..8): the same voxel-centric pass with the class-1 probability of the C-way softmax
-__global__ __launch_bounds__(256) void sw_accumulate_c_kernel(const float* __restrict__ logits, int C, int nb, int p0, int p1, int p2,
-                                                              const int* __restrict__ origins, float* __restrict__ score,
-                                                              float* __restrict__ cnt, int D0, int D1, int D2) {
-    __shared__ int org[3 * 64];
-    for (int i = threadIdx.x; i < 3 * nb; i += 256) org[i] = origins[i];
-    __syncthreads();
-    const long long total = (long long)D0 * D1 * D2;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int c = (int)(i % D2);
-        const long long q = i / D2;
-        const int b_ = (int)(q % D1), a = (int)(q / D1);
-        float s = 0.f, n = 0.f;
-        for (int p = 0; p < nb; ++p) {
-            const int la = a - org[3 * p], lb = b_ - org[3 * p + 1], lc = c - org[3 * p + 2];
-            if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
-                const float* l = logits + ((((long long)p * p0 + la) * p1 + lb) * p2 + lc) * C;
-                float x[8], m = -INFINITY, z = 0.f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < C) { x[k] = l[k]; m = fmaxf(m, x[k]); }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < C) { x[k] = expf(x[k] - m); z += x[k]; }
-                s += x[1] / z;                               // softmax(logits, 1)[1]   (test_3d_patch.py:334-337)
-                n += 1.f;
-            }
-        }
-        if (n > 0.f) { score[i] += s; cnt[i] += n; }
-    }
-}
-
+// C-class models (C in 2..8): class 1 of the max-shifted C-way softmax, for C == 2 too
 extern "C" int dycon_sw_accumulate_c(const float* logits, int C, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                                      float* score, float* cnt, int D0, int D1, int D2, dycon_stream_t stream) {
     DYCON_REQUIRE(logits && origins_dev && score && cnt, "sw_accumulate_c: null pointer");
     DYCON_REQUIRE(C >= 2 && C <= 8, "sw_accumulate_c: C = %d (2..8: class 1 is scored)", C);
-    DYCON_REQUIRE(n_patches > 0 && n_patches <= 64 && p0 > 0 && p1 > 0 && p2 > 0 && D0 >= p0 && D1 >= p1 && D2 >= p2,
-                  "sw_accumulate_c: bad shape (%d patches of %dx%dx%d in %dx%dx%d)", n_patches, p0, p1, p2, D0, D1, D2);
-    long long blocks = ((long long)D0 * D1 * D2 + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    sw_accumulate_c_kernel<<<(int)blocks, 256, 0, stream>>>(logits, C, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2);
-    DYCON_LAUNCH_CHECK();
-    return DYCON_OK;
+    if (int e = sw_check_shape("sw_accumulate_c", n_patches, p0, p1, p2, D0, D1, D2)) return e;
+    return sw_accumulate_launch<1, false>({{logits}}, C, 0, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, nullptr, nullptr,
+                                          stream);
 }
 
 extern "C" int dycon_sw_finalize(const float* score, const float* cnt, long long n, float thresh, uint8_t* label, float* prob,

@@ -1,57 +1,13 @@
 // Multi-class evaluation on the device: the all-class form of the sliding-window evaluator (code/utils/test_3d_patch.py:293-351, which
 // keeps class 1 only, :337-347), the argmax label map (code/train_DyCON_ISLES22.py:364-366) and the C x C confusion counts behind the
-// per-class Dice / Jaccard (code/utils/metrics.py:14-27 cal_dice, code/utils/test_3d_patch.py:496-508).  csrc/eval.hip holds the
-// class-1 evaluator and the binary counts and is left as it is.
+// per-class Dice / Jaccard (code/utils/metrics.py:14-27 cal_dice, code/utils/test_3d_patch.py:496-508).  The all-class accumulate is
+// sw_accumulate_kernel<1, true> (sw_accumulate.h) over the bounding box of a chunk's windows; csrc/eval.hip holds the binary counts.
 //
 // Every kernel here streams its operands once and is HBM-bound; the counts are integers, so they do not depend on the grid.
-#include "common.h"
+#include "sw_accumulate.h"
 
 // first index of the maximum, a NaN counting as the maximum (numpy / torch argmax)
 __device__ __forceinline__ bool argmax_takes(float x, float best) { return x > best || (x != x && best == best); }
-
-// Voxel-centric gather of sw_accumulate_c_kernel (csrc/eval.hip) over the box [lo, hi) of the volume only: every voxel of the box adds
-// the whole C-way softmax of each window of the chunk that covers it, in window order.  score: class-major (C, D0, D1, D2).
-__global__ __launch_bounds__(256) void sw_accumulate_all_kernel(const float* __restrict__ logits, int C, int nb, int p0, int p1, int p2,
-                                                                const int* __restrict__ origins, float* __restrict__ score,
-                                                                float* __restrict__ cnt, int D0, int D1, int D2, int lo0, int lo1, int lo2,
-                                                                int b0, int b1, int b2) {
-    __shared__ int org[3 * 64];
-    for (int i = threadIdx.x; i < 3 * nb; i += 256) org[i] = origins[i];
-    __syncthreads();
-    const long long total = (long long)D0 * D1 * D2, box = (long long)b0 * b1 * b2;
-    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < box; j += (long long)gridDim.x * 256) {
-        const int c = lo2 + (int)(j % b2);
-        const long long q = j / b2;
-        const int b_ = lo1 + (int)(q % b1), a = lo0 + (int)(q / b1);
-        float s[8], n = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] = 0.f;
-        for (int p = 0; p < nb; ++p) {
-            const int la = a - org[3 * p], lb = b_ - org[3 * p + 1], lc = c - org[3 * p + 2];
-            if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
-                const float* l = logits + ((((long long)p * p0 + la) * p1 + lb) * p2 + lc) * C;
-                float x[8], m = -INFINITY, z = 0.f;
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < C) { x[k] = l[k]; m = fmaxf(m, x[k]); }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < C) { x[k] = expf(x[k] - m); z += x[k]; }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (k < C) s[k] += x[k] / z;             // softmax(logits, 1)[k]   (test_3d_patch.py:334-336)
-                n += 1.f;
-            }
-        }
-        if (n > 0.f) {                                       // a voxel of the box that no window of the chunk covers stays untouched
-            const long long i = ((long long)a * D1 + b_) * D2 + c;
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (k < C) score[k * total + i] += s[k];
-            cnt[i] += n;
-        }
-    }
-}
 
 // p_c = score_c / cnt (:344), label = argmax_c p_c.  Each thread reads its voxel's C scores before it writes them: prob may be score.
 __global__ __launch_bounds__(256) void sw_finalize_argmax_kernel(const float* score, const float* __restrict__ cnt, int C, long long n,
@@ -142,17 +98,12 @@ extern "C" int dycon_sw_accumulate_all(const float* logits, int C, int n_patches
                                        dycon_stream_t stream) {
     DYCON_REQUIRE(logits && origins_dev && score && cnt && box_lo && box_hi, "sw_accumulate_all: null pointer");
     DYCON_REQUIRE(C >= 2 && C <= 8, "sw_accumulate_all: C = %d (2..8)", C);
-    DYCON_REQUIRE(n_patches > 0 && n_patches <= 64 && p0 > 0 && p1 > 0 && p2 > 0 && D0 >= p0 && D1 >= p1 && D2 >= p2,
-                  "sw_accumulate_all: bad shape (%d patches of %dx%dx%d in %dx%dx%d)", n_patches, p0, p1, p2, D0, D1, D2);
+    if (int e = sw_check_shape("sw_accumulate_all", n_patches, p0, p1, p2, D0, D1, D2)) return e;
     const int D[3] = {D0, D1, D2};
     for (int a = 0; a < 3; ++a)
         DYCON_REQUIRE(box_lo[a] >= 0 && box_lo[a] < box_hi[a] && box_hi[a] <= D[a],
                       "sw_accumulate_all: box [%d, %d) on axis %d lies outside the volume (extent %d)", box_lo[a], box_hi[a], a, D[a]);
-    const int b0 = box_hi[0] - box_lo[0], b1 = box_hi[1] - box_lo[1], b2 = box_hi[2] - box_lo[2];
-    sw_accumulate_all_kernel<<<capped_blocks((long long)b0 * b1 * b2, 4096), 256, 0, stream>>>(
-        logits, C, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, box_lo[0], box_lo[1], box_lo[2], b0, b1, b2);
-    DYCON_LAUNCH_CHECK();
-    return DYCON_OK;
+    return sw_accumulate_launch<1, true>({{logits}}, C, 0, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, box_lo, box_hi, stream);
 }
 
 extern "C" int dycon_sw_finalize_argmax(const float* score, const float* cnt, int C, long long n, uint8_t* label, float* prob,

@@ -1,13 +1,12 @@
 from . import dycon_losses, losses, monitor, ramps  # noqa: F401
 from . import sliding_window, test_3d_patch  # noqa: F401
 
-# utils/test_3d_patch.py holds the evaluator as it was written for 2-class models and is kept as it is; 2-class nets still run
-# through it.  The reference's test_single_case takes any class count (code/utils/test_3d_patch.py:293-351), so the package binds
-# the class-count form (utils/sliding_window.py, which hands 2-class nets to the original) under that name: test_all_case, the
-# var_all_case_* / test_all_case_* wrappers and every caller of utils.test_3d_patch.test_single_case resolve it at call time.
+# test_3d_patch.py imports test_single_case from sliding_window.py, so this holds already.  It is stated here once more for a
+# test_3d_patch.py of the earlier layout, which defined a 2-class function of that name in the file: with one of those on the path
+# the reference's name must still be the class-count evaluator for test_all_case and the var_all_case_* / test_all_case_* wrappers
 test_3d_patch.test_single_case = sliding_window.test_single_case
 
-# the all-class evaluator and the per-class metrics come beside it under names of their own and rebind nothing
+from . import case_loop  # noqa: E402,F401
 from . import eval_classes  # noqa: E402,F401
 from . import surface  # noqa: E402,F401
 from . import surface_eval  # noqa: E402,F401
@@ -18,7 +17,7 @@ from . import isles_eval  # noqa: E402,F401
 from . import util  # noqa: E402,F401
 
 # the reference's two-model (`_plus`) evaluators, its LA validation loops and two small helpers (code/utils/test_3d_patch.py:14-17,
-# :28-49, :354-476, :488-494) live in utils/ensemble_eval.py; test_3d_patch.py had none of them, so binding them there rebinds nothing
+# :28-49, :354-476, :488-494) live in utils/ensemble_eval.py, which imports test_3d_patch.py; they get the reference's module here
 from . import ensemble_eval  # noqa: E402,F401
 
 for _name in ensemble_eval.REFERENCE_NAMES:

@@ -19,34 +19,26 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import components, sliding_window, surface_eval
+from . import case_loop, components, sliding_window, surface_eval
+
+
+def _device_case(single_case, nms):
+    """the per-case stage of the device-resident loops: `single_case(image)[0]` is the label map as a CUDA tensor"""
+    def per_case(image, label, spacing):
+        pred, _ = single_case(image)
+        return case_loop.binary_case(pred, label, nms, components.largest_component, lambda p, g: surface_eval.calculate_metric_percase(
+            p, g, device_surface=True, voxelspacing=spacing))
+    return per_case
 
 
 def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
                   nms=0, preproc_fn=None, test_save_path=None, label_key="label"):
     """`test_3d_patch.test_all_case` (:251-291): the mean (dice, jaccard, hd95, asd) over the cases."""
-    total = np.zeros(4)
-    n = 0
-    for case in cases:
-        image, label, spacing = surface_eval.read_case(case, label_key)
-        if preproc_fn is not None:
-            image = preproc_fn(image)
-        pred, _ = sliding_window.single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
-        if nms:
-            pred = components.largest_component(pred)
-        if not bool(pred.any()):                               # one flag read back; the empty-prediction convention of :268-271
-            m = (0.0, 0.0, 0.0, 0.0)
-        else:
-            m = surface_eval.calculate_metric_percase(pred, np.asarray(label), device_surface=True, voxelspacing=spacing)
-        if metric_detail:
-            print("%02d,\t%.5f, %.5f, %.5f, %.5f" % ((n,) + tuple(m)))
-        total += np.asarray(m)
-        n += 1
-    avg = total / max(n, 1)
-    if test_save_path is not None:
-        with open(test_save_path + "../performance.txt", "w") as f:
-            f.writelines("average metric is {} \n".format(avg))
-    return avg
+    def single_case(image):
+        return sliding_window.single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
+
+    return case_loop.mean_over_cases(cases, _device_case(single_case, nms), np.zeros(4), label_key, preproc_fn, triples=True,
+                                     detail=case_loop.print_metrics if metric_detail else None, test_save_path=test_save_path)
 
 
 def test_all_case_BraTS19(model, image_list, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, save_result=True,

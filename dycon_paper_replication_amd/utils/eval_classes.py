@@ -1,10 +1,11 @@
 """Multi-class evaluation: the all-class sliding window and per-class metrics (csrc/evalc.hip).
 
-``utils.test_3d_patch.test_single_case`` scores class 1 only, as the reference does (code/utils/test_3d_patch.py:337-347), and stays
+``utils.test_3d_patch.test_single_case`` scores class 1 only, as the reference does (code/utils/test_3d_patch.py:337-347): it is
 the reference-compatible evaluator.  The functions here are the standard multi-class form it was derived from, under names of their
-own: every window adds its whole C-way softmax to a class-major (C, w, h, d) score map, the label map is the argmax of the averaged
-scores (lowest index on ties, as ``np.argmax``), and Dice / Jaccard are taken per foreground class from one C x C confusion matrix
-counted on the device.  HD95 / ASD stay on the host (``test_3d_patch._surface_distances``), one binary pair per class, unless
+own, through the same driver (``sliding_window._sliding_window(..., all_classes=True)``) and the same case loop
+(``case_loop.mean_over_cases``): every window adds its whole C-way softmax to a class-major (C, w, h, d) score map, the label
+map is the argmax of the averaged scores (lowest index on ties, as ``np.argmax``), and Dice / Jaccard are taken per foreground class
+from one C x C confusion matrix counted on the device.  HD95 / ASD stay on the host (``case_loop.hd95_asd``), one binary pair per class, unless
 ``device_surface=True`` asks for the device form (``utils/surface.py``: all classes of a case in one set of launches).
 
     test_single_case_classes(model, image, stride_xy, stride_z, patch_size)     -> (label_map, score_map) as numpy
@@ -17,24 +18,13 @@ counted on the device.  HD95 / ASD stay on the host (``test_3d_patch._surface_di
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from .. import _lib
 from . import components, metrics, surface
-from .test_3d_patch import _read_case, _surface_distances, _windows
-
-
-def chunk_box(chunk, patch_size):
-    """Bounding box (lo, hi), hi exclusive, of the windows of one chunk: the part of the volume dycon_sw_accumulate_all sweeps."""
-    org = np.asarray(chunk, dtype=np.int64).reshape(-1, 3)
-    return tuple(int(v) for v in org.min(0)), tuple(int(v) for v in org.max(0) + np.asarray(patch_size))
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .case_loop import dc_jc as _dc_jc, hd95_asd as _hd95_asd, mean_over_cases as _mean_over_cases
+from .sliding_window import _sliding_window, _stream, chunk_box  # noqa: F401  (chunk_box: public here, tools/eval_bench.py and the tests)
 
 
 def single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
@@ -46,59 +36,19 @@ def single_case_classes_device(model, image, stride_xy, stride_z, patch_size, ba
     C = getattr(model, "n_classes", None)
     if C is not None and C < 2:
         raise ValueError("test_single_case_classes takes the argmax over the classes: the model needs at least 2 classes")
-    img = image if torch.is_tensor(image) else torch.as_tensor(np.asarray(image))
-    img = img.to(dtype=torch.float32)
-    w, h, d = img.shape
-    pads = []
-    for size, p in zip((w, h, d), patch_size):                 # :297-316: centre-pad volumes smaller than the window
-        pad = max(p - size, 0)
-        pads.append((pad // 2, pad - pad // 2))
-    add_pad = any(lo or hi for lo, hi in pads)
-    vol = img.to(dev)
-    if add_pad:
-        vol = torch.nn.functional.pad(vol, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
-    vol = vol.contiguous()
-    ww, hh, dd = vol.shape
-    wins = _windows((ww, hh, dd), patch_size, stride_xy, stride_z)
-    score = cnt = None
-    p0, p1, p2 = patch_size
-    int3 = ctypes.c_int * 3
-    was_training = model.training
-    was_static = getattr(model, "weights_static", None)
-    model.eval()
-    if was_static is not None:
-        model.weights_static = True      # no parameter changes between the windows: pack the weights once (networks/_base.py)
-    try:
-        with torch.no_grad():
-            for i in range(0, len(wins), batch_size):
-                chunk = wins[i:i + batch_size]
-                patches = torch.stack([vol[x:x + p0, y:y + p1, z:z + p2] for x, y, z in chunk]).unsqueeze(1).contiguous()
-                logits = model(patches)[1]                                        # (nb, C, p0, p1, p2), channels-last-3D view
-                if score is None:                                                 # a model that declares no class count: its logits do
-                    if C is None:
-                        C = logits.shape[1]
-                    if not 2 <= C <= 8:
-                        raise ValueError(f"test_single_case_classes takes models of 2..8 classes, got {C}")
-                    score = torch.zeros((C, ww, hh, dd), dtype=torch.float32, device=dev)
-                    cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
-                if logits.shape[1] != C:
-                    raise ValueError(f"the model declares {C} classes and returns logits of {logits.shape[1]}")
-                lg = logits.permute(0, 2, 3, 4, 1).contiguous().float()          # NDHWC (free for the HIP nets' outputs)
-                org = torch.tensor(chunk, dtype=torch.int32).to(dev)
-                lo, hi = chunk_box(chunk, patch_size)
-                _lib.call("dycon_sw_accumulate_all", lg.data_ptr(), C, len(chunk), p0, p1, p2, org.data_ptr(), score.data_ptr(),
-                          cnt.data_ptr(), ww, hh, dd, int3(*lo), int3(*hi), _stream())
-    finally:
-        model.train(was_training)
-        if was_static is not None:
-            model.weights_static = was_static
-    label = torch.empty((ww, hh, dd), dtype=torch.uint8, device=dev)
-    _lib.call("dycon_sw_finalize_argmax", score.data_ptr(), cnt.data_ptr(), C, cnt.numel(), label.data_ptr(), score.data_ptr(),
-              _stream())                                                          # the probabilities replace the sums in place
-    if add_pad:
-        sl = tuple(slice(lo, lo + n) for (lo, _), n in zip(pads, (w, h, d)))
-        label, score = label[sl], score[(slice(None),) + sl]
-    return label, score
+    declared = [C]                                              # a model that declares no class count: its first logits do
+
+    def forward(patches):
+        logits = model(patches)[1]
+        if declared[0] is None:
+            declared[0] = int(logits.shape[1])
+        if not 2 <= declared[0] <= 8:
+            raise ValueError(f"test_single_case_classes takes models of 2..8 classes, got {declared[0]}")
+        if logits.shape[1] != declared[0]:
+            raise ValueError(f"the model declares {declared[0]} classes and returns logits of {logits.shape[1]}")
+        return logits
+
+    return _sliding_window([model], [forward], image, stride_xy, stride_z, patch_size, batch_size, dev, all_classes=True)
 
 
 def test_single_case_classes(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
@@ -129,12 +79,6 @@ def confusion_counts(pred, gt, num_classes):
     if bad:
         raise ValueError(f"{bad} voxels have a prediction or a label outside [0, {C})")
     return out[:C * C].reshape(C, C)
-
-
-def _dc_jc(n_p, n_g, n_i):
-    """medpy.metric.binary.dc / jc from |pred|, |gt|, |pred & gt|: dc is 0 for two empty masks, jc raises ZeroDivisionError"""
-    dc = 2.0 * n_i / float(n_p + n_g) if n_p + n_g else 0.0
-    return dc, float(n_i) / float(n_p + n_g - n_i)
 
 
 def metrics_from_confusion(conf):
@@ -173,9 +117,7 @@ def calculate_metric_perclass(pred, gt, num_classes, device_surface=False, voxel
         if p_host is None:
             p_host = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred)
             g_host = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt)
-        hd1 = _surface_distances(p_host == c, g_host == c, spacing, connectivity)
-        hd2 = _surface_distances(g_host == c, p_host == c, spacing, connectivity)
-        out[c - 1, 2:] = float(np.percentile(np.hstack((hd1, hd2)), 95)), float(hd1.mean())
+        out[c - 1, 2:] = _hd95_asd(p_host == c, g_host == c, spacing, connectivity)
     return out
 
 
@@ -189,32 +131,21 @@ def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), st
     (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is.
     voxelspacing / connectivity go to `calculate_metric_perclass`; a case given as (image, label, spacing) carries its own spacing."""
     surface.normalise_spacing(voxelspacing, connectivity)
-    total = np.zeros((num_classes - 1, 4))
-    n = 0
-    for case in cases:
-        if not isinstance(case, (str, bytes)) and len(case) == 3:
-            image, label, spacing = case
-        else:
-            (image, label), spacing = _read_case(case, label_key), voxelspacing
-        if preproc_fn is not None:
-            image = preproc_fn(image)
+    def per_case(image, label, spacing):
         pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
         if score.shape[0] != num_classes:
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
         if nms:
             pred = components.largest_component_per_class(pred, num_classes)
-        m = calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface, voxelspacing=spacing,
-                                      connectivity=connectivity)
-        if metric_detail:
-            for c, row in enumerate(m, 1):
-                print("%02d, class %d,\t%.5f, %.5f, %.5f, %.5f" % ((n, c) + tuple(row)))
-        total += m
-        n += 1
-    avg = total / max(n, 1)
-    if test_save_path is not None:
-        with open(test_save_path + "../performance.txt", "w") as f:
-            f.writelines("average metric is {} \n".format(avg))
-    return avg
+        return calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface, voxelspacing=spacing,
+                                         connectivity=connectivity)
+
+    def detail(n, m):
+        for c, row in enumerate(m, 1):
+            print("%02d, class %d,\t%.5f, %.5f, %.5f, %.5f" % ((n, c) + tuple(row)))
+
+    return _mean_over_cases(cases, per_case, np.zeros((num_classes - 1, 4)), label_key, preproc_fn, triples=True,
+                            voxelspacing=voxelspacing, detail=detail if metric_detail else None, test_save_path=test_save_path)
 
 
 def isles_pad(shape, patch_size):

@@ -1,9 +1,9 @@
 """The per-case evaluator of ``utils/test_3d_patch.py`` with the opt-in device surface distances (utils/surface.py).
 
-``utils/test_3d_patch.py`` is left as it is and nothing in it is rebound: its ``calculate_metric_percase`` and ``test_all_case`` family
-stay the host-scipy functions they were.  The functions here carry the same names and arguments plus ``device_surface=False``,
-``voxelspacing=None`` and ``connectivity=1`` (medpy's arguments of hd95 / asd).  With all three at their defaults each calls the
-function of ``test_3d_patch.py`` with the arguments it was given.  With the flag on, HD95 and ASD of a case come from one
+``calculate_metric_percase`` and the ``test_all_case`` family of ``utils/test_3d_patch.py`` are the host-scipy functions; the case
+loop and medpy's arithmetic beside them are ``utils/case_loop.py``.  The functions here carry the same names and arguments plus
+``device_surface=False``, ``voxelspacing=None`` and ``connectivity=1`` (medpy's arguments of hd95 / asd).  With all three at their
+defaults each calls the function of ``test_3d_patch.py`` with the arguments it was given.  With the flag on, HD95 and ASD of a case come from one
 ``surface.surface_metrics`` call (csrc/surface.hip for unit spacing and 6-neighbour borders, csrc/surface_spacing.hip otherwise), while
 Dice, Jaccard and the conventions for empty masks are decided from the same device counts either way.  With the flag off and a
 spacing or connectivity given, the host branch passes them to ``test_3d_patch._surface_distances``: millimetres on the host.
@@ -18,19 +18,10 @@ case.  Two-element cases and h5 paths are read as before.
 from __future__ import annotations
 
 import numpy as np
-import torch
 
-from . import surface
+from . import case_loop, surface
 from . import test_3d_patch as _host
-
-
-def read_case(case, label_key, voxelspacing=None):
-    """(image, label, spacing) of one case: an h5 path or (image, label) takes the call's `voxelspacing`, (image, label, spacing) its
-    own"""
-    if not isinstance(case, (str, bytes)) and len(case) == 3:
-        return tuple(case)
-    image, label = _host._read_case(case, label_key)
-    return image, label, voxelspacing
+from .case_loop import read_case  # noqa: F401  (other modules read cases through this name)
 
 
 def calculate_metric_percase(pred, gt, device_surface=False, voxelspacing=None, connectivity=1):
@@ -39,8 +30,7 @@ def calculate_metric_percase(pred, gt, device_surface=False, voxelspacing=None, 
     if not device_surface and spacing is None and connectivity == 1:
         return _host.calculate_metric_percase(pred, gt)
     n_p, n_g, n_i = _host.overlap_counts(pred, gt)
-    dice = 2.0 * n_i / float(n_p + n_g) if n_p + n_g else 0.0
-    jc = float(n_i) / float(n_p + n_g - n_i)               # ZeroDivisionError for two empty masks, as medpy
+    dice, jc = case_loop.dc_jc(n_p, n_g, n_i)
     if n_g == 0:
         return dice, jc, 0.0, 0.0
     if n_p == 0:                                           # what the host path's surface distances raise
@@ -48,10 +38,7 @@ def calculate_metric_percase(pred, gt, device_surface=False, voxelspacing=None, 
     if device_surface:
         m = surface.surface_metrics(pred, gt, voxelspacing=spacing, connectivity=connectivity)[0].tolist()
         return dice, jc, m[0], m[1]
-    p = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred) != 0
-    g = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt) != 0
-    hd1, hd2 = _host._surface_distances(p, g, spacing, connectivity), _host._surface_distances(g, p, spacing, connectivity)
-    return dice, jc, float(np.percentile(np.hstack((hd1, hd2)), 95)), float(hd1.mean())
+    return (dice, jc) + case_loop.hd95_asd(case_loop.host_mask(pred), case_loop.host_mask(gt), spacing, connectivity)
 
 
 def _cases_carry_spacing(cases):
@@ -72,29 +59,14 @@ def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=
         return _host.test_all_case(model, cases, num_classes, patch_size, stride_xy, stride_z, batch_size=batch_size,
                                    metric_detail=metric_detail, nms=nms, preproc_fn=preproc_fn, test_save_path=test_save_path,
                                    label_key=label_key)
-    total = np.zeros(4)
-    n = 0
-    for case in cases:
-        image, label, spacing = read_case(case, label_key, voxelspacing)
-        if preproc_fn is not None:
-            image = preproc_fn(image)
+
+    def per_case(image, label, spacing):
         pred, _ = _host.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, batch_size=batch_size)
-        if nms:
-            pred = _host.getLargestCC(pred)
-        if pred.sum() == 0:
-            m = (0.0, 0.0, 0.0, 0.0)
-        else:
-            m = calculate_metric_percase(pred, np.asarray(label), device_surface=device_surface, voxelspacing=spacing,
-                                         connectivity=connectivity)
-        if metric_detail:
-            print("%02d,\t%.5f, %.5f, %.5f, %.5f" % ((n,) + tuple(m)))
-        total += np.asarray(m)
-        n += 1
-    avg = total / max(n, 1)
-    if test_save_path is not None:
-        with open(test_save_path + "../performance.txt", "w") as f:
-            f.writelines("average metric is {} \n".format(avg))
-    return avg
+        return case_loop.binary_case(pred, label, nms, _host.getLargestCC, lambda p, g: calculate_metric_percase(
+            p, g, device_surface=device_surface, voxelspacing=spacing, connectivity=connectivity))
+
+    return case_loop.mean_over_cases(cases, per_case, np.zeros(4), label_key, preproc_fn, triples=True, voxelspacing=voxelspacing,
+                                     detail=case_loop.print_metrics if metric_detail else None, test_save_path=test_save_path)
 
 
 def test_all_case_BraTS19(model, image_list, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, save_result=True,

@@ -4,90 +4,23 @@
     calculate_metric_percase(pred, gt) -> (dice, jaccard, hd95, asd)                 :496-508
     test_all_case(model, cases, ...)                                                 :251-291
 
-The windows run through the HIP network in batches; score / count maps, the final threshold and the overlap counts behind Dice
-and Jaccard stay on the MI355X (csrc/eval.hip).  HD95 / ASD are surface-distance metrics of medpy (absent here, not vendored by
-the reference): they are restated on scipy.ndimage on the host ("parity unpinned", see oracle/evaluate.py) -- they are
+`test_single_case` is the class-1 evaluator of utils/sliding_window.py, imported here under the reference's name: the windows run
+through the HIP network in batches; score / count maps, the final threshold and the overlap counts behind Dice and Jaccard stay on
+the MI355X (csrc/sw_accumulate.h, csrc/eval.hip).  The loop over cases and medpy's arithmetic are utils/case_loop.py's, for the
+functions here as for surface_eval.py, device_eval.py, ensemble_eval.py and eval_classes.py; it reads `_read_case`,
+`overlap_counts` and `_surface_distances` from this module at call time.  HD95 / ASD are surface-distance metrics of medpy (absent
+here, not vendored by the reference): they are restated on scipy.ndimage on the host ("parity unpinned", see oracle/evaluate.py) -- they are
 per-case diagnostics off the hot path.  The reference reads h5 files (h5py is not available in this image): `test_all_case`
 takes (image, label) arrays, or h5 paths when h5py can be imported.
 """
 from __future__ import annotations
 
-import math
-
 import numpy as np
 import torch
 
-from .. import _lib, ops
-
-
-def _windows(shape, patch_size, stride_xy, stride_z):
-    ww, hh, dd = shape
-    sx = math.ceil((ww - patch_size[0]) / stride_xy) + 1      # :319-321
-    sy = math.ceil((hh - patch_size[1]) / stride_xy) + 1
-    sz = math.ceil((dd - patch_size[2]) / stride_z) + 1
-    out = []
-    for x in range(sx):
-        xs = min(stride_xy * x, ww - patch_size[0])
-        for y in range(sy):
-            ys = min(stride_xy * y, hh - patch_size[1])
-            for z in range(sz):
-                out.append((xs, ys, min(stride_z * z, dd - patch_size[2])))
-    return out
-
-
-def test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=1, batch_size=4, device=None):
-    """image: (w, h, d) numpy array or tensor.  Returns (label_map int64 (w,h,d), score_map float32 (num_classes,w,h,d)) as numpy,
-    like the reference; the class-1 probability fills every channel of score_map (the reference's broadcast, :338-339).
-
-    ``batch_size`` windows go through the network per launch sequence (the reference runs them one by one)."""
-    dev = torch.device(device) if device is not None else next(model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError("test_single_case runs on the MI355X only: move the model to 'cuda'")
-    img = torch.as_tensor(np.asarray(image), dtype=torch.float32)
-    w, h, d = img.shape
-    pads = []
-    for size, p in zip((w, h, d), patch_size):                 # :297-316: centre-pad volumes smaller than the window
-        pad = max(p - size, 0)
-        pads.append((pad // 2, pad - pad // 2))
-    add_pad = any(lo or hi for lo, hi in pads)
-    vol = img.to(dev)
-    if add_pad:
-        vol = torch.nn.functional.pad(vol, (pads[2][0], pads[2][1], pads[1][0], pads[1][1], pads[0][0], pads[0][1]))
-    vol = vol.contiguous()
-    ww, hh, dd = vol.shape
-    wins = _windows((ww, hh, dd), patch_size, stride_xy, stride_z)
-    score = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
-    cnt = torch.zeros_like(score)
-    p0, p1, p2 = patch_size
-    stream = lambda: torch.cuda.current_stream().cuda_stream   # noqa: E731
-    was_training = model.training
-    was_static = getattr(model, "weights_static", None)
-    model.eval()
-    if was_static is not None:
-        model.weights_static = True      # no parameter changes between the windows: pack the weights once (networks/_base.py)
-    try:
-        with torch.no_grad():
-            for i in range(0, len(wins), batch_size):
-                chunk = wins[i:i + batch_size]
-                patches = torch.stack([vol[x:x + p0, y:y + p1, z:z + p2] for x, y, z in chunk]).unsqueeze(1).contiguous()
-                logits = model(patches)[1]                                        # (nb, 2, p0, p1, p2), channels-last-3D view
-                lg = logits.permute(0, 2, 3, 4, 1).contiguous().float()          # NDHWC (free for the HIP nets' outputs)
-                org = torch.tensor(chunk, dtype=torch.int32).to(dev)
-                _lib.call("dycon_sw_accumulate", lg.data_ptr(), len(chunk), p0, p1, p2, org.data_ptr(), score.data_ptr(),
-                          cnt.data_ptr(), ww, hh, dd, stream())
-    finally:
-        model.train(was_training)
-        if was_static is not None:
-            model.weights_static = was_static
-    label = torch.empty((ww, hh, dd), dtype=torch.uint8, device=dev)
-    prob = torch.empty_like(score)
-    _lib.call("dycon_sw_finalize", score.data_ptr(), cnt.data_ptr(), score.numel(), 0.5, label.data_ptr(), prob.data_ptr(), stream())
-    if add_pad:
-        sl = tuple(slice(lo, lo + n) for (lo, _), n in zip(pads, (w, h, d)))
-        label, prob = label[sl], prob[sl]
-    label_map = label.cpu().numpy().astype(np.int64)
-    score_map = np.broadcast_to(prob.cpu().numpy()[None], (num_classes,) + label_map.shape).copy()
-    return label_map, score_map
+from .. import _lib
+from .case_loop import binary_case, dc_jc, hd95_asd, host_mask, mean_dice, mean_over_cases, print_metrics
+from .sliding_window import _windows, single_case_device, test_single_case  # noqa: F401  (the driver and its class-1 evaluator)
 
 
 def overlap_counts(pred, gt):
@@ -118,14 +51,10 @@ def _surface_distances(result, reference, voxelspacing=None, connectivity=1):
 def calculate_metric_percase(pred, gt):
     """(dice, jaccard, hd95, asd) of one case, medpy.metric.binary semantics (code/utils/test_3d_patch.py:496-508)."""
     n_p, n_g, n_i = overlap_counts(pred, gt)
-    dice = 2.0 * n_i / float(n_p + n_g) if n_p + n_g else 0.0
-    jc = float(n_i) / float(n_p + n_g - n_i)               # ZeroDivisionError for two empty masks, as medpy
+    dice, jc = dc_jc(n_p, n_g, n_i)
     if n_g == 0:
         return dice, jc, 0.0, 0.0
-    p = np.asarray(pred.cpu() if torch.is_tensor(pred) else pred) != 0
-    g = np.asarray(gt.cpu() if torch.is_tensor(gt) else gt) != 0
-    hd1, hd2 = _surface_distances(p, g), _surface_distances(g, p)
-    return dice, jc, float(np.percentile(np.hstack((hd1, hd2)), 95)), float(hd1.mean())
+    return (dice, jc) + hd95_asd(host_mask(pred), host_mask(gt))
 
 
 def getLargestCC(segmentation):
@@ -153,25 +82,12 @@ def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=
     """cases: iterable of (image, label) arrays, or of h5 paths with 'image' / `label_key` datasets (needs h5py).
     Returns the mean (dice, jaccard, hd95, asd) over the cases; nms keeps the largest connected component of each prediction,
     preproc_fn is applied to the image first, test_save_path receives `../performance.txt` (code/utils/test_3d_patch.py:251-291)."""
-    total = np.zeros(4)
-    n = 0
-    for case in cases:
-        image, label = _read_case(case, label_key)
-        if preproc_fn is not None:
-            image = preproc_fn(image)
+    def per_case(image, label, spacing):
         pred, _ = test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, batch_size=batch_size)
-        if nms:
-            pred = getLargestCC(pred)
-        m = (0.0, 0.0, 0.0, 0.0) if pred.sum() == 0 else calculate_metric_percase(pred, np.asarray(label))
-        if metric_detail:
-            print("%02d,\t%.5f, %.5f, %.5f, %.5f" % ((n,) + tuple(m)))
-        total += np.asarray(m)
-        n += 1
-    avg = total / max(n, 1)
-    if test_save_path is not None:
-        with open(test_save_path + "../performance.txt", "w") as f:
-            f.writelines("average metric is {} \n".format(avg))
-    return avg
+        return binary_case(pred, label, nms, getLargestCC, calculate_metric_percase)
+
+    return mean_over_cases(cases, per_case, np.zeros(4), label_key, preproc_fn, detail=print_metrics if metric_detail else None,
+                           test_save_path=test_save_path)
 
 
 def _case_list(root_path, list_name, pattern):
@@ -180,35 +96,23 @@ def _case_list(root_path, list_name, pattern):
         return [pattern.format(root=root_path, case=line.strip()) for line in f if line.strip()]
 
 
-def _mean_dice(model, cases, num_classes, patch_size, stride_xy, stride_z, label_key, transpose=None):
-    """validation during training: mean Dice of the sliding-window predictions (the var_all_case_* family, :52-74, :120-141, :188-209).
-    transpose: axis permutation applied to image AND label before the sliding window (BraTS19: (2, 1, 0), :64-65 -- the orientation
-    the training patches have after dataloaders.brats19.SagittalToAxial)."""
-    total, n = 0.0, 0
-    for case in cases:
-        image, label = _read_case(case, label_key)
-        if transpose is not None:
-            image, label = np.transpose(np.asarray(image), transpose), np.transpose(np.asarray(label), transpose)
-        pred, _ = test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes)
-        if pred.sum() != 0:
-            n_p, n_g, n_i = overlap_counts(pred, np.asarray(label))
-            total += 2.0 * n_i / float(n_p + n_g)
-        n += 1
-    return total / max(n, 1)
+def _var_all_case(model, cases, num_classes, patch_size, stride_xy, stride_z, label_key, transpose=None):
+    return mean_dice(cases, lambda image: test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes),
+                     label_key, transpose)
 
 
 # per-dataset wrappers with the reference's names, defaults and on-disk layouts
 def var_all_case_BraTS19(model, root_path, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4):
-    return _mean_dice(model, _case_list(root_path, "val.txt", "{root}/data/{case}.h5"), num_classes, patch_size, stride_xy, stride_z, "label",
-                      transpose=(2, 1, 0))
+    return _var_all_case(model, _case_list(root_path, "val.txt", "{root}/data/{case}.h5"), num_classes, patch_size, stride_xy, stride_z,
+                         "label", transpose=(2, 1, 0))
 
 
 def var_all_case_Pancreas(model, root_path, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4):
-    return _mean_dice(model, _case_list(root_path, "test1.list", "{root}/Pancreas_data/{case}"), num_classes, patch_size, stride_xy, stride_z, "label")
+    return _var_all_case(model, _case_list(root_path, "test1.list", "{root}/Pancreas_data/{case}"), num_classes, patch_size, stride_xy, stride_z, "label")
 
 
 def var_all_case_ISLES22(root_path, model, num_classes, device=None, patch_size=(96, 96, 64), stride_xy=16, stride_z=4):
-    return _mean_dice(model, _case_list(root_path, "val.list", "{root}/{case}.h5"), num_classes, patch_size, stride_xy, stride_z, "mask")
+    return _var_all_case(model, _case_list(root_path, "val.list", "{root}/{case}.h5"), num_classes, patch_size, stride_xy, stride_z, "mask")
 
 
 def test_all_case_BraTS19(model, image_list, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, save_result=True,

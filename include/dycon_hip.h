@@ -565,10 +565,12 @@ int dycon_nonfinite_flag(const float* x, int* flag, dycon_stream_t stream);
  * score / cnt: fp32 maps of the (padded) volume D0 x D1 x D2, zeroed by the caller.  After a batch of n_patches <= 64 windows
  * went through the network, add for every voxel the class-1 softmax of each window covering it (logits: (n_patches, p0, p1, p2, 2)
  * fp32; origins_dev: n_patches x 3 ints, window corner in the volume) and the window count.  Voxel-centric, fixed window order:
- * deterministic although windows overlap. */
+ * deterministic although windows overlap.  This and the three other dycon_sw_accumulate* entry points launch one kernel
+ * (csrc/sw_accumulate.h); class 1 of two logits is scored as 1 / (1 + exp(l0 - l1)) here. */
 int dycon_sw_accumulate(const float* logits, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                         float* score, float* cnt, int D0, int D1, int D2, dycon_stream_t stream);
-/* the same for a C-class model, C in 2..8: logits (n_patches, p0, p1, p2, C) fp32; adds softmax(logits)[1] of the C-way softmax */
+/* the same for a C-class model, C in 2..8: logits (n_patches, p0, p1, p2, C) fp32; adds softmax(logits)[1] of the max-shifted C-way
+ * softmax, for C == 2 too */
 int dycon_sw_accumulate_c(const float* logits, int C, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                           float* score, float* cnt, int D0, int D1, int D2, dycon_stream_t stream);
 /* prob = score / cnt (may be NULL), label = prob > thresh   (:344-345) */
@@ -789,8 +791,9 @@ int dycon_sw_gather(const float* vol, int w, int h, int d, const int* origins_de
                     int p2, float* out, dycon_stream_t stream);
 /* dycon_sw_accumulate for M = 2..4 models with C = 2..8 classes (:459-470): logits0..logits{M-1} are fp32 (n_patches, p0, p1, p2, C),
  * the rest is ignored (pass NULL).  Per covered voxel and class the logits are summed in model order, ((l0 + l1) + l2) + l3, and
- * divided by M ((y1_l + y1_r) / 2, :462); class 1 of the softmax of the mean is added to score and 1 to cnt, with the expressions of
- * dycon_sw_accumulate (C == 2) and dycon_sw_accumulate_c (C > 2): the same model twice gives their bits ((a + a) / 2 == a).
+ * divided by M ((y1_l + y1_r) / 2, :462); class 1 of the softmax of the mean is added to score and 1 to cnt, with the expression of
+ * dycon_sw_accumulate for C == 2 and of dycon_sw_accumulate_c for C > 2 (one kernel body): the same model twice gives their bits
+ * ((a + a) / 2 == a).
  * origins_dev: the n_patches x 3 corners of THIS chunk.  Voxel-centric, fixed window order, no atomics: deterministic. */
 int dycon_sw_accumulate_ens(const float* logits0, const float* logits1, const float* logits2, const float* logits3, int M, int C,
                             int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score, float* cnt, int D0, int D1,

@@ -108,6 +108,42 @@ def test_accumulate_all_and_finalize_against_fp64(C):
     assert torch.equal(label3, label) and torch.equal(alias, prob)
 
 
+@pytest.mark.parametrize("C", [2, 3, 8])
+def test_accumulate_entry_points_share_their_bits(C):
+    """One kernel body serves the four accumulate entry points, so on the same logits, bit for bit: class 1 of dycon_sw_accumulate_c
+    is plane 1 of dycon_sw_accumulate_all over the chunk's box, and a model ensembled with itself (dycon_sw_accumulate_ens, M = 2)
+    is dycon_sw_accumulate for 2 classes and dycon_sw_accumulate_c for more.  The maps hold random values beforehand: whatever a
+    launch does not cover, inside its box or outside, keeps its bits."""
+    rng = np.random.default_rng(300 + C)
+    all0 = rng.random((C,) + VOL).astype(np.float32)
+    cnt0 = rng.integers(1, 4, VOL).astype(np.float32)
+    s_all, c_all = dev(all0), dev(cnt0)
+    s_c, c_c = dev(all0[1]), dev(cnt0)
+    s_one, c_one = dev(all0[1]), dev(cnt0)
+    s_ens, c_ens = dev(all0[1]), dev(cnt0)
+    for name, org in CHUNKS.items():
+        lg = dev((3.0 * rng.standard_normal((len(org),) + PATCH + (C,))).astype(np.float32))
+        origins = dev(np.asarray(org, np.int32))
+        before_all, before_cnt = s_all.clone(), c_all.clone()
+        _accumulate(lg, org, s_all, c_all, C)
+        _lib.call("dycon_sw_accumulate_c", lg.data_ptr(), C, len(org), *PATCH, origins.data_ptr(), s_c.data_ptr(), c_c.data_ptr(), *VOL,
+                  stream())
+        assert torch.equal(s_all[1], s_c) and torch.equal(c_all, c_c), name
+        lo, hi = EC.chunk_box(org, PATCH)
+        outside = torch.ones(VOL, dtype=torch.bool, device=DEV)
+        outside[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = False
+        assert torch.equal(s_all[:, outside], before_all[:, outside]) and torch.equal(c_all[outside], before_cnt[outside]), name
+        assert not torch.equal(c_all, before_cnt), name
+        if C == 2:
+            _lib.call("dycon_sw_accumulate", lg.data_ptr(), len(org), *PATCH, origins.data_ptr(), s_one.data_ptr(), c_one.data_ptr(), *VOL,
+                      stream())
+        else:
+            s_one, c_one = s_c, c_c
+        _lib.call("dycon_sw_accumulate_ens", lg.data_ptr(), lg.data_ptr(), None, None, 2, C, len(org), *PATCH, origins.data_ptr(),
+                  s_ens.data_ptr(), c_ens.data_ptr(), *VOL, stream())
+        assert torch.equal(s_ens, s_one) and torch.equal(c_ens, c_one), name
+
+
 @pytest.mark.parametrize("C", [2, 3, 5, 8])
 def test_exact_tie_yields_the_lower_index(C):
     """two classes with identical logits in every covering window, both the maximum: identical sums, and np.argmax's answer"""

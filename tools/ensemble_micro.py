@@ -3,9 +3,9 @@
 the same box, at the LA geometry: a 175 x 132 x 88 volume, windows 112 x 112 x 80, stride 18 / 4 (45 windows, chunks of 4), two bf16
 V-Nets.
 
-  per chunk  (a) the glue of sliding_window.single_case_device: `batch_size` slice copies, stack, contiguous, and the host-to-device
-                 copy of the chunk's origins;
-             (b) one dycon_sw_gather launch from the origin table uploaded once per case.
+  per chunk  (a) the glue the single-model evaluators had before they shared the ensemble's driver: `batch_size` slice copies, stack,
+                 contiguous, and the host-to-device copy of the chunk's origins;
+             (b) one dycon_sw_gather launch from the origin table uploaded once per case, what sliding_window._sliding_window does.
              Compared bit for bit before anything is timed.  host ms: wall clock of the enqueue loop, no synchronisation inside a
              region.  GPU ms: HIP events around groups of chunks enqueued behind a blocker kernel (back-to-back execution); the
              origin upload of (a) is a synchronous copy that cannot be enqueued behind a blocker, so it is in (a)'s host ms only.
