@@ -166,6 +166,11 @@ SIGNATURES = {
     "dycon_assemble_batch": (I, [P, P, P, I, I, I, I, P, P, I, P]),
     "dycon_sw_gather": (I, [P, I, I, I, P, I, I, I, I, I, I, P, P]),
     "dycon_sw_accumulate_ens": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, I, I, I, P]),
+    "dycon_volume_stats_workspace": (Z, [I, L]),
+    "dycon_volume_stats": (I, [P, I, L, P, P, P, Z, P]),
+    "dycon_normalize_apply": (I, [P, I, L, P, P, P]),
+    "dycon_zoom_workspace": (Z, [I, I, I, I]),
+    "dycon_zoom": (I, [P, I, I, I, I, I, I, I, I, I, P, I, F, P, I, P, Z, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

@@ -120,6 +120,53 @@ class DeviceVolumeCache:
         return (self.images[oi:oi + n].cpu().numpy().reshape(self._shapes[idx]),
                 self.labels[ol:ol + n].cpu().numpy().reshape(self._shapes[idx]))
 
+    @classmethod
+    def from_device_cases(cls, images, labels, max_bytes=None):
+        """A cache of cases that already live on the device (the outputs of preprocessing.preprocess_*_volume): `images` and
+        `labels` are equally long lists of CUDA tensors, a 3-D image and a label of its shape per case.  The two arenas are filled
+        with device-to-device copies on the current stream; offsets, alignment and contents are those `__init__` gives the same
+        cases from the host.  Images are cast to fp32; labels are uint8 or bool as they are, other integer and float dtypes are
+        converted on the device and must hold integers in 0..255 (checked by one device reduction per such case, read back)."""
+        images, labels = list(images), list(labels)
+        if not images:
+            raise ValueError("no cases to cache")
+        if len(images) != len(labels):
+            raise ValueError(f"{len(images)} images and {len(labels)} labels")
+        self = cls.__new__(cls)
+        self.device = images[0].device
+        self._shapes, img_off, lab_off, ni, nl, labs = [], [], [], 0, 0, []
+        for n, (img, lab) in enumerate(zip(images, labels)):
+            if not (torch.is_tensor(img) and torch.is_tensor(lab) and img.is_cuda and img.device == self.device
+                    and lab.device == self.device):
+                raise ValueError(f"case {n}: images and labels are CUDA tensors on one device (host cases go through __init__)")
+            if img.dim() != 3 or img.shape != lab.shape:
+                raise ValueError(f"a case is a 3-D image with a label of its shape, got {tuple(img.shape)} and {tuple(lab.shape)}")
+            if lab.dtype not in (torch.uint8, torch.bool):
+                if lab.dtype.is_complex:
+                    raise ValueError(f"labels must be integers in 0..255, got dtype {lab.dtype}")
+                u = lab.to(torch.uint8)
+                if lab.numel() and not bool(((lab >= 0) & (lab <= 255) & (u == lab)).all()):        # also rejects NaN
+                    raise ValueError("labels must be integers in 0..255")
+                lab = u
+            labs.append(lab)
+            img_off.append(ni)
+            lab_off.append(nl)
+            ni += -(-img.numel() // (_ALIGN // 4)) * (_ALIGN // 4)
+            nl += -(-lab.numel() // _ALIGN) * _ALIGN
+            if max_bytes is not None and 4 * ni + nl > max_bytes:
+                raise ValueError(f"the cache needs more than max_bytes = {max_bytes} (at case {n}: {4 * ni + nl} bytes)")
+            self._shapes.append(tuple(int(v) for v in img.shape))
+        self._nbytes = 4 * ni + nl
+        self._img_off = np.asarray(img_off, dtype=np.int64)
+        self._lab_off = np.asarray(lab_off, dtype=np.int64)
+        self._shape_arr = np.asarray(self._shapes, dtype=np.int32)
+        self.images = torch.zeros(ni, dtype=torch.float32, device=self.device)
+        self.labels = torch.zeros(nl, dtype=torch.uint8, device=self.device)
+        for img, lab, oi, ol in zip(images, labs, img_off, lab_off):
+            self.images[oi:oi + img.numel()].copy_(img.reshape(-1))
+            self.labels[ol:ol + lab.numel()].copy_(lab.reshape(-1))
+        return self
+
 
 def _pads(shape, patch):
     """_pad_to of dataloaders/brats19.py as the reference has it: as soon as ANY axis is <= the patch, ALL three axes are padded by

@@ -1026,6 +1026,34 @@ def copy_segments(tables):
     call("dycon_copy_segments", _h(src_host), _h(dst_host), _h(n_host), nseg, _s())
 
 
+# ------------------------------------------------------------------ preprocessing (csrc/resample.hip; preprocessing.py)
+def volume_stats(vol, stats=None, record=None):
+    """vol: contiguous fp32 (B, X, Y, Z).  stats: (B, 48) uint8 (dycon_volume_stats_t) and / or record: (B, 24) uint8
+    (dycon_norm_record_t), written on the current stream; the one not asked for may be None"""
+    B, V = vol.shape[0], vol[0].numel()
+    ws = torch.empty(int(query("dycon_volume_stats_workspace", B, V)), dtype=torch.uint8, device=vol.device)
+    call("dycon_volume_stats", _p(vol), B, V, _p(stats), _p(record), _p(ws), ws.numel(), _s())
+    return stats, record
+
+
+def normalize_apply(vol, record, out=None):
+    """normalize_image's two fp32 expressions on every voxel of fp32 (B, X, Y, Z), given the samples' records"""
+    out = torch.empty_like(vol) if out is None else out
+    call("dycon_normalize_apply", _p(vol), vol.shape[0], vol[0].numel(), _p(record), _p(out), _s())
+    return out
+
+
+def zoom(vol, target, order, record=None, binarize=None, out_dtype=None):
+    """scipy.ndimage.zoom of every sample of (B, X, Y, Z) fp32 / uint8 to `target`, order 0 or 1; record: normalise on load;
+    binarize: a threshold, order 0, uint8 out.  out_dtype: the input's, or float64 for order 1"""
+    B, X, Y, Z = vol.shape
+    out = torch.empty((B,) + tuple(target), dtype=out_dtype or (torch.uint8 if binarize is not None else vol.dtype), device=vol.device)
+    ws = torch.empty(int(query("dycon_zoom_workspace", order, *target)), dtype=torch.uint8, device=vol.device)
+    call("dycon_zoom", _p(vol), vol.element_size(), B, X, Y, Z, *target, order, _p(record), int(binarize is not None),
+         float(binarize or 0.0), _p(out), out.element_size(), _p(ws), ws.numel(), _s())
+    return out
+
+
 # ------------------------------------------------------------------ optimiser
 def sumsq(g, out):
     call("dycon_sumsq", _p(g), g.numel(), _p(out), _s())

@@ -799,6 +799,74 @@ int dycon_sw_accumulate_ens(const float* logits0, const float* logits1, const fl
                             int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score, float* cnt, int D0, int D1,
                             int D2, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- preprocessing: normalise and zoom (csrc/resample.hip;
+ * code/BraTS19_DataPreprocessing.py:8-31, :175-198; code/ISLES22_DataPreprocessing.py:10-33, :141-159)
+ * All volumes are C-contiguous fp32 (B, X, Y, Z) = B samples of V voxels, every sample with its own statistics.  NaN or infinite
+ * input is out of scope: the results are then unspecified (never an out-of-bounds access).
+ *
+ * dycon_volume_stats: the scalars normalize_image (BraTS19_DataPreprocessing.py:8-31) takes from one volume, per sample:
+ *   n_pos               voxels > 0 (:17 nonzero_mask)
+ *   mean, std           fp64 mean and population standard deviation of those voxels (:19-20), two-pass: the mean first, then the
+ *                       centred squares; 0 when n_pos == 0
+ *   min_pos, max_pos    the smallest and the largest voxel > 0 (0 when there is none)
+ *   min_all, max_all    the extremes over all voxels (what :25-26 read when the z-score is skipped)
+ *   any_nonpos          1 when a voxel <= 0 exists
+ * Sums are fp64 in a fixed order (per-workgroup partials in the workspace, folded by one workgroup: thread t takes partials t,
+ * t + 256, ... in index order, then a fixed tree); counts and flags are integer
+ * atomics; the extremes are integer atomicMax on the bit patterns of the floats (a minimum as the maximum of the complement).  No
+ * floating-point atomic: the same bits on every run, for every alignment of x.
+ * norm (may be NULL, as may stats, not both): the record normalize_image needs, derived without a second reduction:
+ *   mean32, std32 = mean, std rounded once; apply_z = n_pos > 0 && std32 > 0 (:18, :21)
+ *   apply_z:  lo32, hi32 = (min_pos - mean32) / std32, (max_pos - mean32) / std32 in fp32 (the z-score is monotone), widened by
+ *             0.0f when any_nonpos (:22 puts 0 there)
+ *   else:     lo32, hi32 = min_all, max_all (no voxel > 0, or std == 0: the raw values are min-maxed)
+ *   apply_mm = hi32 > lo32 (:28; an all-zero volume, :13, has lo32 == hi32 == 0 and comes back unchanged)
+ * One hipMemsetAsync and three launches on the stream; no allocation, no host synchronisation.  workspace: 8-byte aligned.
+ *
+ * dycon_normalize_apply: out = normalize_image(x) at full resolution given the records: per voxel, in fp32, each operation rounded
+ * on its own (no fused multiply-add): z = x > 0 ? (x - mean32) / std32 : 0 when apply_z (:22), then (z - lo32) / (hi32 - lo32)
+ * when apply_mm (:29).  out may alias x.
+ *
+ * dycon_zoom: scipy.ndimage.zoom(x, [Xo / X, Yo / Y, Zo / Z], order, mode="constant", cval=0, grid_mode=False) of every sample
+ * (BraTS19_DataPreprocessing.py:190-194, ISLES22_DataPreprocessing.py:151-155), order 0 or 1.  Along an axis n_in -> n_out the
+ * source coordinate of output index i is c = double(i) * (double(n_in - 1) / double(n_out - 1)) (0 when n_out == 1): IEEE doubles,
+ * one multiplication, nothing fused.
+ *   order 0   source index floor(c + 0.5) per axis, clamped to n_in - 1: a gather, bit for bit scipy's.  src fp32 -> out fp32
+ *             or src uint8 -> out uint8 (src_bytes == out_bytes).  binarize != 0: out is uint8 and holds (float(value) > threshold)
+ *             as 0 / 1, from an fp32 or a uint8 source: `(seg > 0).astype(np.uint8)` (BraTS :180) or `mask > 0.5` (ISLES :145)
+ *             taken on load; the reference's `> 0.5` after the zoom (BraTS :198) then changes nothing.
+ *   order 1   f = floor(c), t = c - f; eight taps in the order x, y, z with z fastest; a tap index beyond the last voxel is clamped
+ *             (its weight is zero or rounding dust); weight (wx * wy) * wz with w = 1 - t or t; acc += weight * double(value)
+ *             from 0.0, all in fp64, each multiplication and addition rounded on its own; rounded once to fp32 (out_bytes 4, what
+ *             scipy returns for an fp32 input) or kept (out_bytes 8).  src fp32.  Differs from scipy by its summation order only.
+ *   norm      (may be NULL; fp32 source, not with binarize) one record per sample: every tap value first goes through the two
+ *             expressions of dycon_normalize_apply, so the full-resolution normalised volume is never written.
+ * A first small launch writes the per-axis index / weight tables to the workspace, the second gathers: four consecutive z outputs
+ * per thread, 16-byte stores (4-byte for uint8) when Zo % 4 == 0 and out is that aligned, element stores otherwise; the source
+ * side assumes no alignment beyond the element's.  Rejected before any launch: a null pointer, an order outside {0, 1}, a
+ * non-positive axis or batch, a type combination not listed above, a workspace smaller than dycon_zoom_workspace (0 for
+ * arguments it rejects).  Bitwise reproducible. */
+typedef struct {
+    long long n_pos;
+    double mean, std;
+    float min_pos, max_pos, min_all, max_all;
+    int any_nonpos, reserved;
+} dycon_volume_stats_t;
+typedef struct {
+    int apply_z;
+    float mean32, std32;
+    int apply_mm;
+    float lo32, hi32;
+} dycon_norm_record_t;
+size_t dycon_volume_stats_workspace(int B, long long V);
+int dycon_volume_stats(const float* x, int B, long long V, dycon_volume_stats_t* stats, dycon_norm_record_t* norm, void* workspace,
+                       size_t ws_bytes, dycon_stream_t stream);
+int dycon_normalize_apply(const float* x, int B, long long V, const dycon_norm_record_t* norm, float* out, dycon_stream_t stream);
+size_t dycon_zoom_workspace(int order, int Xo, int Yo, int Zo);
+int dycon_zoom(const void* src, int src_bytes, int B, int X, int Y, int Z, int Xo, int Yo, int Zo, int order,
+               const dycon_norm_record_t* norm, int binarize, float threshold, void* out, int out_bytes, void* workspace,
+               size_t ws_bytes, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
