@@ -171,6 +171,8 @@ SIGNATURES = {
     "dycon_normalize_apply": (I, [P, I, L, P, P, P]),
     "dycon_zoom_workspace": (Z, [I, I, I, I]),
     "dycon_zoom": (I, [P, I, I, I, I, I, I, I, I, I, P, I, F, P, I, P, Z, P]),
+    "dycon_assemble_batch_rot": (I, [P, P, P, I, I, I, I, P, P, I, P, I, I, P]),
+    "dycon_rotate_nearest": (I, [P, P, I, I, I, I, P, P, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

@@ -1,3 +1,6 @@
-"""Data path mirror; device_cache: the training set resident in HBM, batches assembled by one HIP launch."""
+"""Data path mirror; device_cache: the training set resident in HBM, batches assembled by one HIP launch;
+device_augment: RandomRot, CreateOnehotLabel and RandomNoise on that path."""
+from .device_augment import (ROT_PLAN_DTYPE, apply_rot_plan_host, assemble_batch_rot, draw_plan_rot, rotate_nearest,   # noqa: F401
+                             rotation_of)
 from .device_cache import (PLAN_DTYPE, DeviceBatchLoader, DeviceVolumeCache, apply_plan_host, assemble_batch,   # noqa: F401
                            draw_plan)

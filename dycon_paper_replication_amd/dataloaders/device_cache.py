@@ -6,6 +6,8 @@
     apply_plan_host(plan, images, labels)                     host: numpy restatement of the kernel (the CPU-testable twin)
     assemble_batch(cache, plan, out, label_dtype)             device: dycon_assemble_batch, one launch per 16 samples
     DeviceBatchLoader(cache, batch_sampler, patch_size, ...)  iterates a batch sampler, yields {"image", "label"} device batches
+                                                              (rot / onehot / noise_sigma: RandomRot, CreateOnehotLabel and
+                                                              RandomNoise on the same path, device_augment.py)
 
 The training pipelines of the reference's three scripts are `[SagittalToAxial ->] RandomCrop -> RandomRotFlip -> ToTensor`
 (train_DyCON_BraTS19.py:238-242, train_DyCON_Pancreas.py:150-167, train_DyCON_ISLES22.py:165-190) in DataLoader worker processes.
@@ -203,18 +205,8 @@ def _rotflip_crop_record(shape, patch):
     return (ox, oy, d1 - pad[2]), k, axis
 
 
-def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False, order="crop_rotflip"):
-    """The plan of one batch: a PLAN_DTYPE record per entry of `indices` (case numbers into `shapes`).
-
-    Pure host code.  Consumes ``np.random`` exactly as ``RandomCrop(patch_size)`` followed by ``RandomRotFlip()`` do for each index
-    in order: three randint for the crop, bounds from the PADDED shape, then k, then the axis (rot_flip=False: the crop only,
-    k = 0, no flip).  center=True gives the CenterCrop origin and draws nothing.  An odd k with patch_size[0] != patch_size[1]
-    raises ValueError: the rotated crop would not have the patch's shape (the reference could not stack such a batch either).
-
-    order="rotflip_crop" is the LA pipelines' ``RandomRotFlip()`` BEFORE ``RandomCrop(patch_size)``: k, the axis, then the three
-    crop offsets from the rotated, then padded shape, translated into the same records (`_rotflip_crop_record`).  It needs
-    rot_flip=True and center=False (without the rotation, or with a drawn-nothing centre crop, there is one order only); an odd k
-    still needs a square patch, because the kernel rotates the crop."""
+def _plan_args(patch_size, rot_flip, center, order):
+    """-> the patch as a tuple of ints; ValueError for arguments draw_plan rejects"""
     patch = tuple(int(v) for v in patch_size)
     if len(patch) != 3 or min(patch) <= 0:
         raise ValueError(f"patch_size must be three positive sizes, got {patch_size}")
@@ -222,15 +214,15 @@ def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False, order="c
         raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
     if order == "rotflip_crop" and (center or not rot_flip):
         raise ValueError("order='rotflip_crop' is the order of RandomRotFlip and RandomCrop: it needs rot_flip=True and center=False")
-    plan = np.zeros(len(indices), dtype=PLAN_DTYPE)
-    for n, idx in enumerate(indices):
-        shape = shapes[idx]
-        if order == "rotflip_crop":
-            origin, k, axis = _rotflip_crop_record(shape, patch)
-            if (k & 1) and patch[0] != patch[1]:
-                raise ValueError(f"rot90 by k = {k} of a {patch[0]} x {patch[1]} crop does not give a {patch[0]} x {patch[1]} patch")
-            plan[n] = (idx, origin, k, axis, patch)
-            continue
+    return patch
+
+
+def _draw_record(shape, patch, rot_flip, center, order):
+    """One sample of either order (the drawing code of draw_plan, shared with device_augment.draw_plan_rot)
+    -> (origin in stored coordinates, k, axis)"""
+    if order == "rotflip_crop":
+        origin, k, axis = _rotflip_crop_record(shape, patch)
+    else:
         pad = _pads(shape, patch)
         w, h, d = (shape[a] + 2 * pad[a] for a in range(3))
         k, axis = 0, -1
@@ -243,9 +235,28 @@ def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False, order="c
             if rot_flip:
                 k = np.random.randint(0, 4)
                 axis = np.random.randint(0, 2)
-        if (k & 1) and patch[0] != patch[1]:
-            raise ValueError(f"rot90 by k = {k} of a {patch[0]} x {patch[1]} crop does not give a {patch[0]} x {patch[1]} patch")
-        plan[n] = (idx, (w1 - pad[0], h1 - pad[1], d1 - pad[2]), k, axis, patch)
+        origin = (w1 - pad[0], h1 - pad[1], d1 - pad[2])
+    if (k & 1) and patch[0] != patch[1]:
+        raise ValueError(f"rot90 by k = {k} of a {patch[0]} x {patch[1]} crop does not give a {patch[0]} x {patch[1]} patch")
+    return origin, k, axis
+
+
+def draw_plan(shapes, indices, patch_size, rot_flip=True, center=False, order="crop_rotflip"):
+    """The plan of one batch: a PLAN_DTYPE record per entry of `indices` (case numbers into `shapes`).
+
+    Pure host code.  Consumes ``np.random`` exactly as ``RandomCrop(patch_size)`` followed by ``RandomRotFlip()`` do for each index
+    in order: three randint for the crop, bounds from the PADDED shape, then k, then the axis (rot_flip=False: the crop only,
+    k = 0, no flip).  center=True gives the CenterCrop origin and draws nothing.  An odd k with patch_size[0] != patch_size[1]
+    raises ValueError: the rotated crop would not have the patch's shape (the reference could not stack such a batch either).
+
+    order="rotflip_crop" is the LA pipelines' ``RandomRotFlip()`` BEFORE ``RandomCrop(patch_size)``: k, the axis, then the three
+    crop offsets from the rotated, then padded shape, translated into the same records (`_rotflip_crop_record`).  It needs
+    rot_flip=True and center=False (without the rotation, or with a drawn-nothing centre crop, there is one order only); an odd k
+    still needs a square patch, because the kernel rotates the crop."""
+    patch = _plan_args(patch_size, rot_flip, center, order)
+    plan = np.zeros(len(indices), dtype=PLAN_DTYPE)
+    for n, idx in enumerate(indices):
+        plan[n] = (idx, *_draw_record(shapes[idx], patch, rot_flip, center, order), patch)
     return plan
 
 
@@ -332,17 +343,34 @@ class DeviceBatchLoader:
     ``transform = Compose([RandomCrop(patch_size), RandomRotFlip(), ToTensor()])`` bit for bit (label_dtype=torch.int64 for
     ToTensor's dtype; `pre=SagittalToAxial()` on the cache for the BraTS chain; rot_flip=False leaves RandomRotFlip out).  The
     reference's multi-worker stream is not reproducible by anything.  order="rotflip_crop": the LA chain
-    ``Compose([RandomRotFlip(), RandomCrop(patch_size), ToTensor()])`` (dataloaders/la_heart.py) instead, see `draw_plan`."""
+    ``Compose([RandomRotFlip(), RandomCrop(patch_size), ToTensor()])`` (dataloaders/la_heart.py) instead, see `draw_plan`.
 
-    def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8, order="crop_rotflip"):
+    The remaining augmentations of the reference's loader modules (dataloaders/device_augment.py); with their defaults nothing of
+    the above changes, calls, draws and bits:
+      rot=True          ``RandomRot()`` in front of either chain (scipy's nearest-neighbour rotation by randint(-20, 20) degrees),
+                        still bit for bit the host chain: `draw_plan_rot` / `assemble_batch_rot`.
+      onehot=C          adds "onehot_label" (B, C, w, h, d) of onehot_dtype (int64 as ToTensor leaves it, uint8 or float32):
+                        ``CreateOnehotLabel(C)`` in front of ToTensor, written by the same launch.
+      noise_sigma=s     the reference's ``RandomNoise(0, s)``: image + clip(s * N(0, 1), -2 s, 2 s).  The normal deviates are the
+                        library's counter-based Philox stream, NOT ``np.random.randn``'s, so this one is equal in distribution
+                        only: the image of batch number n of the loader's life is
+                        ``ops.add_noise(image, None, s, 2 * s, noise_seed, n << 32)`` of the noise-free image.  A non-zero mu is
+                        not offered.  The noisy image is written into the ring buffer, so the two-batch lifetime holds."""
+
+    def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8, order="crop_rotflip",
+                 rot=False, onehot=None, onehot_dtype=torch.int64, noise_sigma=None, noise_seed=0):
         if order not in ORDERS:
             raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
         if order == "rotflip_crop" and not rot_flip:
             raise ValueError("order='rotflip_crop' needs rot_flip=True")
+        if noise_sigma is not None and not noise_sigma > 0:
+            raise ValueError(f"noise_sigma must be None or positive, got {noise_sigma}")
         self.cache, self.batch_sampler, self.rot_flip, self.label_dtype = cache, batch_sampler, rot_flip, label_dtype
         self.order = order
+        self.rot, self.onehot, self.onehot_dtype = bool(rot), onehot, onehot_dtype
+        self.noise_sigma, self.noise_seed = noise_sigma, int(noise_seed)
         self.patch_size = tuple(int(v) for v in patch_size)
-        self._ring, self._n = [None, None], 0
+        self._ring, self._n, self._clean = [None, None], 0, None
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -350,15 +378,41 @@ class DeviceBatchLoader:
     def plans(self):
         """the host side of an epoch on its own: the plan of every batch, in order (draws as iterating the loader does)"""
         shapes = self.cache.shapes
+        if self.rot:
+            from .device_augment import draw_plan_rot
         for batch in self.batch_sampler:
-            yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
+            if self.rot:
+                yield draw_plan_rot(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
+            else:
+                yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
+
+    def _assemble(self, plan, out):
+        if self.rot or self.onehot is not None:
+            from .device_augment import assemble_batch_rot
+            return assemble_batch_rot(self.cache, plan, out=out, label_dtype=self.label_dtype, onehot=self.onehot,
+                                      onehot_dtype=self.onehot_dtype)
+        return assemble_batch(self.cache, plan, out=out, label_dtype=self.label_dtype)
 
     def __iter__(self):
         for plan in self.plans():
             slot = self._n & 1
-            self._n += 1
             buf = self._ring[slot]
             if buf is None or buf["image"].shape[0] != len(plan):
                 buf = None
-            self._ring[slot] = buf = assemble_batch(self.cache, plan, out=buf, label_dtype=self.label_dtype)
+            if self.noise_sigma is None:
+                self._ring[slot] = buf = self._assemble(plan, buf)
+            else:
+                # the batch is assembled with its image in a buffer of the loader's own, the noisy image goes into the ring
+                if buf is None:
+                    buf = self._assemble(plan, None)
+                    self._clean, buf["image"] = buf["image"], torch.empty_like(buf["image"])
+                else:
+                    if self._clean.shape != buf["image"].shape:
+                        self._clean = torch.empty_like(buf["image"])
+                    self._assemble(plan, {**buf, "image": self._clean})
+                clean, s = self._clean, float(self.noise_sigma)
+                _lib.call("dycon_add_noise", clean.data_ptr(), None, buf["image"].data_ptr(), _lib.F32, clean.numel(), s, 2 * s,
+                          self.noise_seed, self._n << 32, ops._s())
+                self._ring[slot] = buf
+            self._n += 1
             yield buf

@@ -6,7 +6,8 @@
     TwoStreamBatchSampler, ThreeStreamBatchSampler                                              :250-308
 
 Transforms shared with dataloaders/brats19.py / pancreas.py (identical np.random call order).  `RandomRot` rotates by a random
-integer angle with scipy.ndimage (nearest neighbour, no reshape) -- host arrays only.  Parity unpinned (see pancreas.py).
+integer angle: scipy.ndimage (nearest neighbour, no reshape) for host arrays, the same rotation bit for bit in HIP for CUDA tensors
+(device_augment.rotate_nearest); inside a DeviceBatchLoader it is the `rot=True` argument.  Parity unpinned (see pancreas.py).
 """
 from __future__ import annotations
 
@@ -47,6 +48,9 @@ class RandomRot(object):
     def __call__(self, sample):
         from scipy import ndimage
         angle = np.random.randint(-20, 20)
+        if torch.is_tensor(sample["image"]) and sample["image"].is_cuda:
+            from .device_augment import rotate_nearest
+            return {"image": rotate_nearest(sample["image"], angle), "label": rotate_nearest(sample["label"], angle)}
         f = lambda a: ndimage.rotate(np.asarray(a), angle, order=0, reshape=False)   # noqa: E731
         return {"image": f(sample["image"]), "label": f(sample["label"])}
 

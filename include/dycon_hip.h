@@ -867,6 +867,44 @@ int dycon_zoom(const void* src, int src_bytes, int B, int X, int Y, int Z, int X
                const dycon_norm_record_t* norm, int binarize, float threshold, void* out, int out_bytes, void* workspace,
                size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- augmentation on the batch-assembly path (csrc/augment.hip;
+ * dataloaders/device_augment.py; the reference's RandomRot and CreateOnehotLabel, code/dataloaders/isles22.py:24-28, :198-234)
+ * dycon_assemble_batch_rot is dycon_assemble_batch with `scipy.ndimage.rotate(case, angle, order=0, reshape=False)` in front of
+ * the chain and, optionally, the one-hot label written in the same launch.  The rotated volume never exists: the crop origin,
+ * k and flip_axis of a job address the ROTATED volume (which keeps the stored shape), and for an output voxel whose index
+ * (rx, ry, rz) into it lies inside [0,X) x [0,Y) x [0,Z) (outside: the reference's zero pad, 0) the source is found as scipy
+ * finds it, in fp64, every operation rounded on its own (no fused multiply-add):
+ *     cx = ((0.0 + rx * m[0]) + ry * m[1]) + off[0]          cy = ((0.0 + rx * m[2]) + ry * m[3]) + off[1]
+ *     cx < 0 | cx > X - 1 | cy < 0 | cy > Y - 1  ->  0       (mode='constant': the test comes before the rounding)
+ *     otherwise  stored[floor(cx + 0.5), floor(cy + 0.5), rz]
+ * with m = [[c, s], [-s, c]] (c, s = cosdg, sindg of the angle) row-major and off = ctr - m @ ctr, ctr = ([X, Y] - 1) / 2, all
+ * computed by the caller.  rotate == 0: m and off are ignored, (rx, ry) is the source, the bits are dycon_assemble_batch's.
+ * out_onehot (may be NULL): (njobs, onehot_classes, P0, P1, P2) of element size onehot_bytes = 1 (uint8), 4 (fp32) or 8 (int64);
+ * plane c holds label == c as 0 / 1, a label >= onehot_classes sets no plane; onehot_classes in 1..8.
+ * Rejected before any launch: what dycon_assemble_batch rejects, a non-finite m / off of a rotating job, onehot_classes or
+ * onehot_bytes out of range.  16-byte stores when P2 % 4 == 0 and every output is aligned for them, element stores otherwise.
+ *
+ * dycon_rotate_nearest: the same rotation of one whole C-contiguous (X, Y, Z) device volume of 1-, 4- or 8-byte elements into
+ * `out` (which must not overlap `in`); it moves bytes, so any type of those sizes goes through.  m (4) and off (2) are host
+ * pointers read at call time.  The source coordinates come from the same device function as the batch kernel's.
+ * Both are pure gathers: bitwise reproducible. */
+typedef struct {
+    long long image_off, label_off; /* the fields of dycon_crop_job_t ... */
+    int X, Y, Z;
+    int ox, oy, oz;                 /* crop origin in the rotated volume (= stored coordinates) */
+    int k;
+    int flip_axis;
+    double m[4];                    /* ... and the rotation: matrix, row-major */
+    double off[2];                  /* offset */
+    int rotate;                     /* 0: no rotation (m, off ignored) */
+    int reserved;
+} dycon_rot_job_t;
+int dycon_assemble_batch_rot(const float* images, const uint8_t* labels, const dycon_rot_job_t* jobs_host, int njobs, int P0, int P1,
+                             int P2, float* out_image, void* out_label, int label_bytes, void* out_onehot, int onehot_classes,
+                             int onehot_bytes, dycon_stream_t stream);
+int dycon_rotate_nearest(const void* in, void* out, int elem_bytes, int X, int Y, int Z, const double* m, const double* off,
+                         dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
