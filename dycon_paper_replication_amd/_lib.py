@@ -166,6 +166,8 @@ SIGNATURES = {
     "dycon_assemble_batch": (I, [P, P, P, I, I, I, I, P, P, I, P]),
     "dycon_sw_gather": (I, [P, I, I, I, P, I, I, I, I, I, I, P, P]),
     "dycon_sw_accumulate_ens": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, I, I, I, P]),
+    "dycon_sw_gather_mirror": (I, [P, I, I, I, P, I, I, I, I, I, I, P, P]),
+    "dycon_sw_accumulate_weighted": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, I, I, I, P, P, P]),
     "dycon_volume_stats_workspace": (Z, [I, L]),
     "dycon_volume_stats": (I, [P, I, L, P, P, P, Z, P]),
     "dycon_normalize_apply": (I, [P, I, L, P, P, P]),

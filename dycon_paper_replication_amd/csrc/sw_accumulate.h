@@ -1,5 +1,6 @@
 // The accumulate pass of the sliding-window evaluators (code/utils/test_3d_patch.py:293-351, :415-476), shared by the entry points of
-// csrc/eval.hip (one model, class 1), csrc/evalc.hip (one model, all classes) and csrc/ensemble.hip (2..4 models, class 1).
+// csrc/eval.hip (one model, class 1), csrc/evalc.hip (one model, all classes) and csrc/ensemble.hip (2..4 models, class 1; the
+// weighted form of all of them).
 //
 // The reference copies every patch's softmax to the host and accumulates score / count maps with numpy slicing.  Here the maps
 // stay in HBM: after a batch of patches went through the network, one voxel-centric pass adds, for every voxel of a box of the
@@ -24,17 +25,28 @@ template <int M> __device__ __forceinline__ float sw_logit(const SwLogits& in, l
     return x;
 }
 
+// What the weighted form (BLEND) reads beside the logits: g[a][i], fp32, is the importance of local coordinate i of window axis a.
+// The plain instantiations carry the empty struct: no argument is loaded and no code is generated for it.
+template <bool BLEND> struct SwBlend {};
+template <> struct SwBlend<true> {
+    const float* g[3];
+};
+
 // Sweeps the box [lo, lo + b) of the volume D0 x D1 x D2.  ALL: every class of the C-way softmax goes to the class-major score map
 // (C, D0, D1, D2); otherwise class 1 goes to score (D0, D1, D2).  pair (C == 2, class 1 only): the two-logit expression
 // 1 / (1 + exp(l0 - l1)) instead of the max-shifted softmax; dycon_sw_accumulate and the ensemble of 2-class models score that way.
-template <int M, bool ALL>
+// BLEND (dycon_sw_accumulate_weighted): `origins` holds (ox, oy, oz, mask) per entry.  The window went through the network flipped
+// along every axis whose mask bit is set, so the logits of local coordinate l sit at the mirrored coordinate; the entry adds
+// w * p to score and w to cnt with w = (g0[la] * g1[lb]) * g2[lc] at the UNmirrored coordinate.  Unit tables and mask 0 give the
+// plain form's bits: 1 * p and n + 1 are exact.
+template <int M, bool ALL, bool BLEND = false>
 __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, int pair, int nb, int p0, int p1, int p2,
                                                             const int* __restrict__ origins, float* __restrict__ score,
                                                             float* __restrict__ cnt, int D0, int D1, int D2, int lo0, int lo1, int lo2,
-                                                            int b0, int b1, int b2) {
-    constexpr int S = ALL ? 8 : 1;
-    __shared__ int org[3 * 64];
-    for (int i = threadIdx.x; i < 3 * nb; i += 256) org[i] = origins[i];
+                                                            int b0, int b1, int b2, SwBlend<BLEND> bl) {
+    constexpr int S = ALL ? 8 : 1, E = BLEND ? 4 : 3;
+    __shared__ int org[E * 64];
+    for (int i = threadIdx.x; i < E * nb; i += 256) org[i] = origins[i];
     __syncthreads();
     const long long total = (long long)D0 * D1 * D2, box = (long long)b0 * b1 * b2;
     for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < box; j += (long long)gridDim.x * 256) {
@@ -45,11 +57,21 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, 
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = 0.f;
         for (int p = 0; p < nb; ++p) {
-            const int la = a - org[3 * p], lb = b_ - org[3 * p + 1], lc = c - org[3 * p + 2];
+            const int la = a - org[E * p], lb = b_ - org[E * p + 1], lc = c - org[E * p + 2];
             if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
-                const long long at = ((((long long)p * p0 + la) * p1 + lb) * p2 + lc) * C;
+                int ma = la, mb = lb, mc = lc;
+                float wt = 1.f;                              // the plain form: 1.f * p folds to p
+                if constexpr (BLEND) {
+                    const int mask = org[E * p + 3];
+                    if (mask & 1) ma = p0 - 1 - la;
+                    if (mask & 2) mb = p1 - 1 - lb;
+                    if (mask & 4) mc = p2 - 1 - lc;
+                    wt = (bl.g[0][la] * bl.g[1][lb]) * bl.g[2][lc];
+                }
+                const long long at = ((((long long)p * p0 + ma) * p1 + mb) * p2 + mc) * C;
                 if (!ALL && pair) {
-                    s[0] += 1.f / (1.f + __expf(sw_logit<M>(in, at) - sw_logit<M>(in, at + 1)));   // softmax(logits)[1]  (:334-337)
+                    const float pr = 1.f / (1.f + __expf(sw_logit<M>(in, at) - sw_logit<M>(in, at + 1)));   // softmax(logits)[1]  (:334-337)
+                    s[0] += wt * pr;
                 } else {
                     float x[8], m = -INFINITY, z = 0.f;
 #pragma unroll
@@ -61,12 +83,12 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, 
                     if constexpr (ALL) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k)
-                            if (k < C) s[k] += x[k] / z;     // softmax(logits, 1)[k]   (:334-336)
+                            if (k < C) s[k] += wt * (x[k] / z);        // softmax(logits, 1)[k]   (:334-336)
                     } else {
-                        s[0] += x[1] / z;                    // softmax(logits, 1)[1]   (:334-337)
+                        s[0] += wt * (x[1] / z);                   // softmax(logits, 1)[1]   (:334-337)
                     }
                 }
-                n += 1.f;
+                n += wt;
             }
         }
         if (n > 0.f) {                                       // a voxel of the box that no window of the chunk covers stays untouched
@@ -87,18 +109,18 @@ static int sw_check_shape(const char* who, int n_patches, int p0, int p1, int p2
 }
 
 // box_lo == nullptr: the whole volume
-template <int M, bool ALL>
+template <int M, bool ALL, bool BLEND = false>
 static int sw_accumulate_launch(const SwLogits& in, int C, int pair, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                                 float* score, float* cnt, int D0, int D1, int D2, const int* box_lo, const int* box_hi,
-                                dycon_stream_t stream) {
+                                dycon_stream_t stream, SwBlend<BLEND> bl = {}) {
     const int zero[3] = {0, 0, 0}, D[3] = {D0, D1, D2};
     const int* lo = box_lo ? box_lo : zero;
     const int* hi = box_lo ? box_hi : D;
     const int b0 = hi[0] - lo[0], b1 = hi[1] - lo[1], b2 = hi[2] - lo[2];
     long long blocks = ((long long)b0 * b1 * b2 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    sw_accumulate_kernel<M, ALL><<<(int)blocks, 256, 0, stream>>>(in, C, pair, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2,
-                                                                  lo[0], lo[1], lo[2], b0, b1, b2);
+    sw_accumulate_kernel<M, ALL, BLEND><<<(int)blocks, 256, 0, stream>>>(in, C, pair, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1,
+                                                                         D2, lo[0], lo[1], lo[2], b0, b1, b2, bl);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }

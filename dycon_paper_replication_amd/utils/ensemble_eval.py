@@ -15,6 +15,10 @@ is not the mean of the models' probability maps.  The windows go through the dri
 end.  Score and count maps never leave the device.  The models run one after the other on the current stream.  An ensemble of a
 model with itself gives `single_case_device`'s bits at the same `batch_size`: one kernel body serves both (csrc/sw_accumulate.h).
 The case loops are `case_loop.mean_over_cases` and `case_loop.mean_dice`.
+
+`single_case_ensemble_device` and `single_case_plus_device` take ``blend=`` (`sliding_window.Blend`: Gaussian importance weighting,
+mirror test-time augmentation).  The functions under the reference's names keep the reference's parameter lists and blend as the
+reference does.
 """
 from __future__ import annotations
 
@@ -60,10 +64,11 @@ def _check_models(models):
     return models
 
 
-def single_case_ensemble_device(models, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
+def single_case_ensemble_device(models, image, stride_xy, stride_z, patch_size, batch_size=4, device=None, *, blend=None):
     """(label uint8 (w, h, d), prob float32 (w, h, d)) as CUDA tensors: the sliding window of `test_single_case_plus` over 2..4
     models with one class count (2..8; otherwise ValueError).  prob: class 1 of the softmax of the models' mean logits, averaged over
-    the windows covering a voxel; label = prob > 0.5.  image: (w, h, d) numpy array or tensor.  batch_size: 1..64 windows per chunk."""
+    the windows covering a voxel; label = prob > 0.5.  image: (w, h, d) numpy array or tensor.  batch_size: 1..64 windows per chunk.
+    blend: None or a `sliding_window.Blend`."""
     models = _check_models(models)
     if not 1 <= int(batch_size) <= 64:
         raise ValueError(f"batch_size must be in 1..64, got {batch_size}")
@@ -88,12 +93,13 @@ def single_case_ensemble_device(models, image, stride_xy, stride_z, patch_size, 
         return forward
 
     return sliding_window._sliding_window(models, [forward_of(m) for m in models], image, stride_xy, stride_z, patch_size, batch_size,
-                                          dev)
+                                          dev, blend=blend)
 
 
-def single_case_plus_device(model_l, model_r, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
+def single_case_plus_device(model_l, model_r, image, stride_xy, stride_z, patch_size, batch_size=4, device=None, *, blend=None):
     """`single_case_ensemble_device` of the reference's pair (model_l, model_r)"""
-    return single_case_ensemble_device((model_l, model_r), image, stride_xy, stride_z, patch_size, batch_size=batch_size, device=device)
+    return single_case_ensemble_device((model_l, model_r), image, stride_xy, stride_z, patch_size, batch_size=batch_size, device=device,
+                                       blend=blend)
 
 
 def test_single_case_plus(model_l, model_r, image, stride_xy, stride_z, patch_size, device=None, num_classes=1, batch_size=4):

@@ -27,9 +27,9 @@ from .case_loop import dc_jc as _dc_jc, hd95_asd as _hd95_asd, mean_over_cases a
 from .sliding_window import _sliding_window, _stream, chunk_box  # noqa: F401  (chunk_box: public here, tools/eval_bench.py and the tests)
 
 
-def single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
+def single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None, *, blend=None):
     """The device-resident form of `test_single_case_classes`: (label uint8 (w, h, d), score float32 (C, w, h, d)) as CUDA tensors,
-    without host copies."""
+    without host copies.  blend: None or a `sliding_window.Blend`."""
     dev = torch.device(device) if device is not None else next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("test_single_case_classes runs on the MI355X only: move the model to 'cuda'")
@@ -48,16 +48,17 @@ def single_case_classes_device(model, image, stride_xy, stride_z, patch_size, ba
             raise ValueError(f"the model declares {declared[0]} classes and returns logits of {logits.shape[1]}")
         return logits
 
-    return _sliding_window([model], [forward], image, stride_xy, stride_z, patch_size, batch_size, dev, all_classes=True)
+    return _sliding_window([model], [forward], image, stride_xy, stride_z, patch_size, batch_size, dev, all_classes=True, blend=blend)
 
 
-def test_single_case_classes(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None):
+def test_single_case_classes(model, image, stride_xy, stride_z, patch_size, batch_size=4, device=None, *, blend=None):
     """image: (w, h, d) numpy array or tensor.  Returns (label_map int64 (w, h, d) with values in [0, C), score_map float32
     (C, w, h, d)) as numpy: score_map[c] is the class-c probability averaged over the windows that cover a voxel, label_map its argmax
     over c.  Padding, window list, crop and the handling of the model's mode are `sliding_window.test_single_case`'s; C is the
     model's `n_classes`, or the channel count of its logits when it declares none.  `batch_size` windows go through the network per
-    launch sequence."""
-    label, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, device=device)
+    launch sequence.  blend: None, the plain mean over the windows, or a `sliding_window.Blend`."""
+    label, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, device=device,
+                                              blend=blend)
     return label.cpu().numpy().astype(np.int64), score.cpu().numpy()
 
 
@@ -123,16 +124,17 @@ def calculate_metric_perclass(pred, gt, num_classes, device_surface=False, voxel
 
 def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
                           preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, nms=0, voxelspacing=None,
-                          connectivity=1):
+                          connectivity=1, *, blend=None):
     """`test_all_case` (code/utils/test_3d_patch.py:251-291) with the all-class evaluator: cases as there; returns the mean (C-1, 4)
     (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  device_surface is
     passed to `calculate_metric_perclass`.  The reference defines `nms` for the class-1 map only (:19-26, :266-267); `nms` here is
     its per-class extension: each foreground class of the prediction keeps its largest component
     (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is.
-    voxelspacing / connectivity go to `calculate_metric_perclass`; a case given as (image, label, spacing) carries its own spacing."""
+    voxelspacing / connectivity go to `calculate_metric_perclass`; a case given as (image, label, spacing) carries its own spacing.
+    blend goes to `single_case_classes_device`."""
     surface.normalise_spacing(voxelspacing, connectivity)
     def per_case(image, label, spacing):
-        pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size)
+        pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, blend=blend)
         if score.shape[0] != num_classes:
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
         if nms:

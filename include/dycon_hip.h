@@ -799,6 +799,33 @@ int dycon_sw_accumulate_ens(const float* logits0, const float* logits1, const fl
                             int n_patches, int p0, int p1, int p2, const int* origins_dev, float* score, float* cnt, int D0, int D1,
                             int D2, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- blended sliding window (csrc/ensemble.hip, csrc/sw_accumulate.h;
+ * utils/sliding_window.py Blend).  Not in the reference: Gaussian importance weighting and mirror test-time augmentation.
+ * An ENTRY is a window in one orientation: 4 ints (ox, oy, oz, mask), the corner as in dycon_sw_gather and bit a of mask set when the
+ * window goes through the network flipped along window axis a (0, 1, 2 = dims 2, 3, 4 of the batch).  The table is device data and
+ * is not validated: bits of mask above bit 2 are ignored, and no origin or mask can make a kernel read or write out of bounds.
+ *
+ * dycon_sw_gather_mirror: dycon_sw_gather for entries [first, first + n) of a table of n_entries x 4 ints on the device:
+ * out[e, 0, i, j, k] = the zero-padded volume at (ox + (mask & 1 ? p0 - 1 - i : i), oy + (mask & 2 ? p1 - 1 - j : j),
+ * oz + (mask & 4 ? p2 - 1 - k : k)).  Same conventions and the same checks; a pure copy: np.flip of the padded volume's slices, bit
+ * for bit. */
+int dycon_sw_gather_mirror(const float* vol, int w, int h, int d, const int* entries_dev, int n_entries, int first, int n, int p0,
+                           int p1, int p2, float* out, dycon_stream_t stream);
+/* The accumulate of dycon_sw_accumulate / _c / _ens / _all (one kernel body, csrc/sw_accumulate.h) for n <= 64 entries, entries_dev the
+ * n x 4 ints of THIS chunk.  M in 1..4 models with logits0..logits{M-1} fp32 (n, p0, p1, p2, C), the rest NULL; C in 2..8.
+ * all_classes 0: score (D0, D1, D2) receives class 1 of the softmax of the mean logits, by the two-logit expression for C == 2 and
+ * the max-shifted softmax otherwise; all_classes 1 (needs M == 1): score is class-major (C, D0, D1, D2) and receives every class.
+ * g0 / g1 / g2: device fp32 tables of p0 / p1 / p2 positive importances.  For every voxel of the box [box_lo, box_hi) (host int[3];
+ * both NULL: the whole volume) and every entry of the chunk, in order, that covers it at local coordinate (la, lb, lc): the
+ * probability p is formed from the logits at the mirrored coordinate (mask & 1 ? p0 - 1 - la : la, ...), which un-flips the
+ * network's output, and with w = (g0[la] * g1[lb]) * g2[lc] in fp32 the voxel's sums take s += w * p (fused or not), n += w; then
+ * score += s, cnt += n.  Voxel-centric, no atomics: deterministic.  Unit tables and mask 0 give the bits of the unweighted entry
+ * points.  dycon_sw_finalize / dycon_sw_finalize_argmax divide as before. */
+int dycon_sw_accumulate_weighted(const float* logits0, const float* logits1, const float* logits2, const float* logits3, int M, int C,
+                                 int all_classes, int n, int p0, int p1, int p2, const int* entries_dev, const float* g0,
+                                 const float* g1, const float* g2, float* score, float* cnt, int D0, int D1, int D2,
+                                 const int* box_lo, const int* box_hi, dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- preprocessing: normalise and zoom (csrc/resample.hip;
  * code/BraTS19_DataPreprocessing.py:8-31, :175-198; code/ISLES22_DataPreprocessing.py:10-33, :141-159)
  * All volumes are C-contiguous fp32 (B, X, Y, Z) = B samples of V voxels, every sample with its own statistics.  NaN or infinite
