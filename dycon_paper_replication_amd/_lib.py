@@ -168,6 +168,12 @@ SIGNATURES = {
     "dycon_sw_accumulate_ens": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, I, I, I, P]),
     "dycon_sw_gather_mirror": (I, [P, I, I, I, P, I, I, I, I, I, I, P, P]),
     "dycon_sw_accumulate_weighted": (I, [P, P, P, P, I, I, I, I, I, I, I, P, P, P, P, P, P, I, I, I, P, P, P]),
+    # csrc/uncertainty.hip: the moments form of dycon_sw_accumulate_weighted, dycon_sw_finalize_argmax plus the four uncertainty maps,
+    # and the counts behind ECE / Brier / NLL / error detection (utils/uncertainty.py)
+    "dycon_sw_accumulate_moments": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P, P, I, I, I, P, P, P]),
+    "dycon_sw_finalize_uncertainty": (I, [P, P, P, P, I, L, P, P, P, P, P, P]),
+    "dycon_calibration_workspace": (Z, [L, I]),
+    "dycon_calibration_counts": (I, [P, P, P, P, F, I, L, I, P, P, P, Z, P]),
     "dycon_volume_stats_workspace": (Z, [I, L]),
     "dycon_volume_stats": (I, [P, I, L, P, P, P, Z, P]),
     "dycon_normalize_apply": (I, [P, I, L, P, P, P]),

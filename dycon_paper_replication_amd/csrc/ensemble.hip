@@ -113,7 +113,7 @@ extern "C" int dycon_sw_accumulate_ens(const float* logits0, const float* logits
     DYCON_REQUIRE(origins_dev && score && cnt, "sw_accumulate_ens: null pointer");
     if (int e = sw_check_shape("sw_accumulate_ens", n_patches, p0, p1, p2, D0, D1, D2)) return e;
     const auto launch = M == 2 ? sw_accumulate_launch<2, false> : M == 3 ? sw_accumulate_launch<3, false> : sw_accumulate_launch<4, false>;
-    return launch(in, C, C == 2, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, nullptr, nullptr, stream, {});
+    return launch(in, C, C == 2, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1, D2, nullptr, nullptr, stream, {}, {});
 }
 
 // Every accumulate above with importance tables and mirrored windows: sw_accumulate_kernel<M, ALL, true>
@@ -140,5 +140,5 @@ extern "C" int dycon_sw_accumulate_weighted(const float* logits0, const float* l
                         : M == 2    ? sw_accumulate_launch<2, false, true>
                         : M == 3    ? sw_accumulate_launch<3, false, true>
                                     : sw_accumulate_launch<4, false, true>;
-    return launch(in, C, !all_classes && C == 2, n, p0, p1, p2, entries_dev, score, cnt, D0, D1, D2, box_lo, box_hi, stream, {{g0, g1, g2}});
+    return launch(in, C, !all_classes && C == 2, n, p0, p1, p2, entries_dev, score, cnt, D0, D1, D2, box_lo, box_hi, stream, {{g0, g1, g2}}, {});
 }

@@ -32,6 +32,15 @@ template <> struct SwBlend<true> {
     const float* g[3];
 };
 
+// What the moments form (MOM, dycon_sw_accumulate_moments, csrc/uncertainty.hip) writes beside score and cnt: hsum (D0, D1, D2) takes
+// w * H(p) and sq (C, D0, D1, D2) takes w * p[k]^2 of every entry, the sums behind the uncertainty maps.  The other instantiations
+// carry the empty struct, as with SwBlend.
+template <bool MOM> struct SwMoments {};
+template <> struct SwMoments<true> {
+    float* hsum;
+    float* sq;
+};
+
 // Sweeps the box [lo, lo + b) of the volume D0 x D1 x D2.  ALL: every class of the C-way softmax goes to the class-major score map
 // (C, D0, D1, D2); otherwise class 1 goes to score (D0, D1, D2).  pair (C == 2, class 1 only): the two-logit expression
 // 1 / (1 + exp(l0 - l1)) instead of the max-shifted softmax; dycon_sw_accumulate and the ensemble of 2-class models score that way.
@@ -39,12 +48,16 @@ template <> struct SwBlend<true> {
 // along every axis whose mask bit is set, so the logits of local coordinate l sit at the mirrored coordinate; the entry adds
 // w * p to score and w to cnt with w = (g0[la] * g1[lb]) * g2[lc] at the UNmirrored coordinate.  Unit tables and mask 0 give the
 // plain form's bits: 1 * p and n + 1 are exact.
-template <int M, bool ALL, bool BLEND = false>
+// MOM (needs M == 1, ALL, BLEND): every entry is a member of the voxel's ensemble.  Beside s[k] += w * p[k] and n += w, the same
+// expressions in the same order, the voxel keeps m2[k] += w * (p[k] * p[k]) and hs += w * H(p), H(p) = -sum_k p[k] ln p[k] over the
+// classes in order, a class with p[k] == 0 adding nothing (a saturated softmax has entropy 0, not NaN): 2C + 2 accumulators.
+template <int M, bool ALL, bool BLEND = false, bool MOM = false>
 __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, int pair, int nb, int p0, int p1, int p2,
                                                             const int* __restrict__ origins, float* __restrict__ score,
                                                             float* __restrict__ cnt, int D0, int D1, int D2, int lo0, int lo1, int lo2,
-                                                            int b0, int b1, int b2, SwBlend<BLEND> bl) {
-    constexpr int S = ALL ? 8 : 1, E = BLEND ? 4 : 3;
+                                                            int b0, int b1, int b2, SwBlend<BLEND> bl, SwMoments<MOM> mo) {
+    static_assert(!MOM || (M == 1 && ALL && BLEND), "the moments form is the weighted all-class accumulate of one model");
+    constexpr int S = ALL ? 8 : 1, E = BLEND ? 4 : 3, Q = MOM ? 8 : 1;
     __shared__ int org[E * 64];
     for (int i = threadIdx.x; i < E * nb; i += 256) org[i] = origins[i];
     __syncthreads();
@@ -56,6 +69,9 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, 
         float s[S], n = 0.f;
 #pragma unroll
         for (int k = 0; k < S; ++k) s[k] = 0.f;
+        float m2[Q], hs = 0.f;                                // MOM only
+#pragma unroll
+        for (int k = 0; k < Q; ++k) m2[k] = 0.f;
         for (int p = 0; p < nb; ++p) {
             const int la = a - org[E * p], lb = b_ - org[E * p + 1], lc = c - org[E * p + 2];
             if ((unsigned)la < (unsigned)p0 && (unsigned)lb < (unsigned)p1 && (unsigned)lc < (unsigned)p2) {
@@ -80,7 +96,18 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, 
 #pragma unroll
                     for (int k = 0; k < 8; ++k)
                         if (k < C) { x[k] = expf(x[k] - m); z += x[k]; }
-                    if constexpr (ALL) {
+                    if constexpr (MOM) {
+                        float h = 0.f;
+#pragma unroll
+                        for (int k = 0; k < 8; ++k)
+                            if (k < C) {
+                                const float pk = x[k] / z;
+                                s[k] += wt * pk;                       // the ALL branch's expression
+                                m2[k] += wt * (pk * pk);
+                                if (pk > 0.f) h -= pk * logf(pk);
+                            }
+                        hs += wt * h;
+                    } else if constexpr (ALL) {
 #pragma unroll
                         for (int k = 0; k < 8; ++k)
                             if (k < C) s[k] += wt * (x[k] / z);        // softmax(logits, 1)[k]   (:334-336)
@@ -97,6 +124,12 @@ __global__ __launch_bounds__(256) void sw_accumulate_kernel(SwLogits in, int C, 
             for (int k = 0; k < S; ++k)
                 if (k < C) score[k * total + i] += s[k];
             cnt[i] += n;
+            if constexpr (MOM) {
+#pragma unroll
+                for (int k = 0; k < Q; ++k)
+                    if (k < C) mo.sq[k * total + i] += m2[k];
+                mo.hsum[i] += hs;
+            }
         }
     }
 }
@@ -109,18 +142,18 @@ static int sw_check_shape(const char* who, int n_patches, int p0, int p1, int p2
 }
 
 // box_lo == nullptr: the whole volume
-template <int M, bool ALL, bool BLEND = false>
+template <int M, bool ALL, bool BLEND = false, bool MOM = false>
 static int sw_accumulate_launch(const SwLogits& in, int C, int pair, int n_patches, int p0, int p1, int p2, const int* origins_dev,
                                 float* score, float* cnt, int D0, int D1, int D2, const int* box_lo, const int* box_hi,
-                                dycon_stream_t stream, SwBlend<BLEND> bl = {}) {
+                                dycon_stream_t stream, SwBlend<BLEND> bl = {}, SwMoments<MOM> mo = {}) {
     const int zero[3] = {0, 0, 0}, D[3] = {D0, D1, D2};
     const int* lo = box_lo ? box_lo : zero;
     const int* hi = box_lo ? box_hi : D;
     const int b0 = hi[0] - lo[0], b1 = hi[1] - lo[1], b2 = hi[2] - lo[2];
     long long blocks = ((long long)b0 * b1 * b2 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    sw_accumulate_kernel<M, ALL, BLEND><<<(int)blocks, 256, 0, stream>>>(in, C, pair, n_patches, p0, p1, p2, origins_dev, score, cnt, D0, D1,
-                                                                         D2, lo[0], lo[1], lo[2], b0, b1, b2, bl);
+    sw_accumulate_kernel<M, ALL, BLEND, MOM><<<(int)blocks, 256, 0, stream>>>(in, C, pair, n_patches, p0, p1, p2, origins_dev, score, cnt, D0,
+                                                                              D1, D2, lo[0], lo[1], lo[2], b0, b1, b2, bl, mo);
     DYCON_LAUNCH_CHECK();
     return DYCON_OK;
 }

@@ -157,14 +157,33 @@ class HipSegNet(nn.Module):
         self._drop_calls += 1
         return DropoutSpec("philox", seed=self._drop_seed, offset=self._drop_calls * (1 << 24))
 
-    def forward(self, x, turnoff_drop=False):
-        """turnoff_drop: dropout is off for this call (VNet.py:231-239); the default issues the launches it always issued"""
+    def _check_input(self, x):
         if not x.is_cuda:
             raise RuntimeError("HipSegNet runs on the MI355X only (no CPU fallback): move the module and input to 'cuda'")
         if x.dim() != 5 or x.shape[1] != self.in_channels:
             raise ValueError(f"expected (B,{self.in_channels},D,H,W), got {tuple(x.shape)}")
         if any(s % 16 for s in x.shape[2:]):
             raise ValueError("D, H, W must be divisible by 16")
+
+    @torch.no_grad()
+    def forward_mc(self, x, seed, offset):
+        """One Monte-Carlo dropout pass (utils/uncertainty.py): the dropout sites draw Philox masks from (seed, offset) whatever the
+        module's mode, every normalisation runs in inference mode (BatchNorm reads its running statistics and updates nothing,
+        `num_batches_tracked` included), nothing is recorded for a backward.  The same (seed, offset) gives the same bits; offsets of
+        two passes must differ by at least 1 << 42 (the sites of one pass spread over that range, engine.Engine._drop_elements).
+        Returns (None, logits, features) as `forward` does, without the tanh map."""
+        if not self.has_dropout:
+            raise ValueError("forward_mc needs a model with dropout sites: this one was built with has_dropout=False")
+        self._check_input(x)
+        eng = self._engine()
+        eng.repack()
+        logits, feats, _ = eng.forward(to_ndhwc(x.float().contiguous()), training=False, record=False,
+                                       dropout=DropoutSpec("philox", seed=int(seed), offset=int(offset)), update_bn=False)
+        return None, to_ncdhw_view(logits), to_ncdhw_view(feats)
+
+    def forward(self, x, turnoff_drop=False):
+        """turnoff_drop: dropout is off for this call (VNet.py:231-239); the default issues the launches it always issued"""
+        self._check_input(x)
         if not turnoff_drop:
             return _NetFunction.apply(x.float().contiguous(), self, *self.parameters())
         has_dropout, self.has_dropout = self.has_dropout, False

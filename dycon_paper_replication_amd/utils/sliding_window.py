@@ -22,6 +22,7 @@ the C-way softmax is scored, as the reference does (:337-347).  A 1-class model 
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import dataclasses
 import math
@@ -145,6 +146,23 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+@contextlib.contextmanager
+def _eval_static(models):
+    """The models in eval mode with static weights inside the block; each one's `training` flag and `weights_static` are put back."""
+    saved = [(m, m.training, getattr(m, "weights_static", None)) for m in models]
+    try:
+        for m, _, was_static in saved:
+            m.eval()
+            if was_static is not None:
+                m.weights_static = True      # no parameter changes between the windows: pack the weights once (networks/_base.py)
+        yield
+    finally:
+        for m, was_training, was_static in saved:
+            m.train(was_training)
+            if was_static is not None:
+                m.weights_static = was_static
+
+
 def _sliding_window(models, forwards, image, stride_xy, stride_z, patch_size, batch_size, dev, all_classes=False, blend=None):
     """The windows of `image` ((w, h, d) numpy array or tensor) through `forwards`, one callable per model of `models` that maps the
     (nb, 1, p0, p1, p2) windows of a chunk to (nb, C, p0, p1, p2) logits; the callers validate the models' outputs in there.  The
@@ -174,46 +192,35 @@ def _sliding_window(models, forwards, image, stride_xy, stride_z, patch_size, ba
     cnt = torch.zeros((ww, hh, dd), dtype=torch.float32, device=dev)
     score = None
     int3 = ctypes.c_int * 3
-    saved = [(m, m.training, getattr(m, "weights_static", None)) for m in models]
-    try:
-        for m, _, was_static in saved:
-            m.eval()
-            if was_static is not None:
-                m.weights_static = True      # no parameter changes between the windows: pack the weights once (networks/_base.py)
-        with torch.no_grad():
-            for i in range(0, n_rows, batch_size):
-                nb = min(batch_size, n_rows - i)
-                patches = torch.empty((nb, 1, p0, p1, p2), dtype=torch.float32, device=dev)
-                _lib.call("dycon_sw_gather" if blend is None else "dycon_sw_gather_mirror", vol.data_ptr(), w, h, d, origins.data_ptr(),
-                          n_rows, i, nb, p0, p1, p2, patches.data_ptr(), _stream())
-                # (nb, C, p0, p1, p2) channels-last-3D views -> NDHWC fp32 (free for the HIP nets' outputs)
-                lgs = [f(patches).permute(0, 2, 3, 4, 1).contiguous().float() for f in forwards]
-                C = lgs[0].shape[-1]
-                if score is None:
-                    score = torch.zeros(((C,) if all_classes else ()) + (ww, hh, dd), dtype=torch.float32, device=dev)
-                if blend is not None:
-                    lo, hi = chunk_box(entries[i:i + nb, :3], (p0, p1, p2))
-                    ptrs = [t.data_ptr() for t in lgs] + [None] * (MAX_MODELS - len(lgs))
-                    _lib.call("dycon_sw_accumulate_weighted", *ptrs, len(lgs), C, int(all_classes), nb, p0, p1, p2,
-                              origins.data_ptr() + 16 * i, *(g.data_ptr() for g in tables), score.data_ptr(), cnt.data_ptr(), ww, hh, dd,
-                              int3(*lo), int3(*hi), _stream())
-                    continue
-                maps = (nb, p0, p1, p2, origins.data_ptr() + 12 * i, score.data_ptr(), cnt.data_ptr(), ww, hh, dd)
-                if all_classes:
-                    lo, hi = chunk_box(wins[i:i + nb], (p0, p1, p2))
-                    _lib.call("dycon_sw_accumulate_all", lgs[0].data_ptr(), C, *maps, int3(*lo), int3(*hi), _stream())
-                elif len(lgs) > 1:
-                    ptrs = [t.data_ptr() for t in lgs] + [None] * (MAX_MODELS - len(lgs))
-                    _lib.call("dycon_sw_accumulate_ens", *ptrs, len(lgs), C, *maps, _stream())
-                elif C == 2:
-                    _lib.call("dycon_sw_accumulate", lgs[0].data_ptr(), *maps, _stream())
-                else:
-                    _lib.call("dycon_sw_accumulate_c", lgs[0].data_ptr(), C, *maps, _stream())
-    finally:
-        for m, was_training, was_static in saved:
-            m.train(was_training)
-            if was_static is not None:
-                m.weights_static = was_static
+    with _eval_static(models), torch.no_grad():
+        for i in range(0, n_rows, batch_size):
+            nb = min(batch_size, n_rows - i)
+            patches = torch.empty((nb, 1, p0, p1, p2), dtype=torch.float32, device=dev)
+            _lib.call("dycon_sw_gather" if blend is None else "dycon_sw_gather_mirror", vol.data_ptr(), w, h, d, origins.data_ptr(),
+                      n_rows, i, nb, p0, p1, p2, patches.data_ptr(), _stream())
+            # (nb, C, p0, p1, p2) channels-last-3D views -> NDHWC fp32 (free for the HIP nets' outputs)
+            lgs = [f(patches).permute(0, 2, 3, 4, 1).contiguous().float() for f in forwards]
+            C = lgs[0].shape[-1]
+            if score is None:
+                score = torch.zeros(((C,) if all_classes else ()) + (ww, hh, dd), dtype=torch.float32, device=dev)
+            if blend is not None:
+                lo, hi = chunk_box(entries[i:i + nb, :3], (p0, p1, p2))
+                ptrs = [t.data_ptr() for t in lgs] + [None] * (MAX_MODELS - len(lgs))
+                _lib.call("dycon_sw_accumulate_weighted", *ptrs, len(lgs), C, int(all_classes), nb, p0, p1, p2,
+                          origins.data_ptr() + 16 * i, *(g.data_ptr() for g in tables), score.data_ptr(), cnt.data_ptr(), ww, hh, dd,
+                          int3(*lo), int3(*hi), _stream())
+                continue
+            maps = (nb, p0, p1, p2, origins.data_ptr() + 12 * i, score.data_ptr(), cnt.data_ptr(), ww, hh, dd)
+            if all_classes:
+                lo, hi = chunk_box(wins[i:i + nb], (p0, p1, p2))
+                _lib.call("dycon_sw_accumulate_all", lgs[0].data_ptr(), C, *maps, int3(*lo), int3(*hi), _stream())
+            elif len(lgs) > 1:
+                ptrs = [t.data_ptr() for t in lgs] + [None] * (MAX_MODELS - len(lgs))
+                _lib.call("dycon_sw_accumulate_ens", *ptrs, len(lgs), C, *maps, _stream())
+            elif C == 2:
+                _lib.call("dycon_sw_accumulate", lgs[0].data_ptr(), *maps, _stream())
+            else:
+                _lib.call("dycon_sw_accumulate_c", lgs[0].data_ptr(), C, *maps, _stream())
     label = torch.empty((ww, hh, dd), dtype=torch.uint8, device=dev)
     if all_classes:
         prob = score                                            # the probabilities replace the sums in place

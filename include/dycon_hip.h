@@ -826,6 +826,44 @@ int dycon_sw_accumulate_weighted(const float* logits0, const float* logits1, con
                                  const float* g1, const float* g2, float* score, float* cnt, int D0, int D1, int D2,
                                  const int* box_lo, const int* box_hi, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- uncertainty maps and calibration (csrc/uncertainty.hip,
+ * csrc/sw_accumulate.h; utils/uncertainty.py).  Not in the reference, whose evaluator keeps the mean softmax only
+ * (code/utils/test_3d_patch.py:334-347); restated here are the textbook definitions over the MEMBERS of a voxel's ensemble, every
+ * entry that covers it (window x orientation x model x Monte-Carlo pass), each with its own softmax p_e and weight w_e:
+ *   H(p) = -sum_k p[k] ln p[k], a term with p[k] == 0 counting as 0 (saturated logits give entropy 0, never NaN).
+ *
+ * dycon_sw_accumulate_moments: dycon_sw_accumulate_weighted with M = 1, all_classes = 1 (same entries, tables, box, mirrored read,
+ * fixed entry order, no atomics; score and cnt receive the same bits) that also adds, per voxel and covering entry,
+ * w * H(p_e) to hsum (D0, D1, D2) and w * (p_e[k] * p_e[k]) to sq, class-major (C, D0, D1, D2).  All in fp32. */
+int dycon_sw_accumulate_moments(const float* logits, int C, int n, int p0, int p1, int p2, const int* entries_dev, const float* g0,
+                                const float* g1, const float* g2, float* score, float* cnt, float* hsum, float* sq, int D0, int D1,
+                                int D2, const int* box_lo, const int* box_hi, dycon_stream_t stream);
+/* Over n voxels: label and prob exactly as dycon_sw_finalize_argmax forms them (prob = score / cnt written over score, lowest index
+ * on ties), and four fp32 maps of n values:
+ *   entropy = H(prob)    expected_entropy = hsum / cnt    mutual_info = max(0, entropy - expected_entropy)
+ *   variance = sum_k max(0, sq[k] / cnt - prob[k]^2) */
+int dycon_sw_finalize_uncertainty(float* score, const float* cnt, const float* hsum, const float* sq, int C, long long n,
+                                  uint8_t* label, float* entropy, float* expected_entropy, float* mutual_info, float* variance,
+                                  dycon_stream_t stream);
+/* The counts behind ECE / MCE (equal-width confidence bins, Guo et al. 2017), the Brier score, the negative log-likelihood and the
+ * error-detection curves, of prob (C, V) fp32 class-major against label (V) uint8; mask (V) uint8, may be NULL: only voxels with
+ * mask != 0 are scored.  K bins, 1..64.  Per scored voxel: confidence c = max_k prob[k], prediction = its first index, bin =
+ * min(K - 1, (int)(c * (float)K)), the product one fp32 multiplication (never fused).
+ *   counts (4K + 2 int64, device, zeroed here): n[K] | correct[K] | unc_hist[0][K] (correct voxels) | unc_hist[1][K] (wrong) |
+ *           n_scored | scored voxels whose label lies outside [0, C), counted nowhere else (the rule of dycon_class_confusion)
+ *   sums   (K + 2 fp64, device, written): conf_sum[K] = sum of c per bin | brier_sum = sum_v sum_k (prob[k] - [k == label])^2 |
+ *           nll_sum = sum_v -ln max(prob[label], 1e-12); every term formed in fp64, nothing fused
+ *   unc (V) fp32, may be NULL (the two histograms stay 0): an uncertainty per voxel with upper bound u_max > 0; its bin is
+ *           min(K - 1, (int)(u / u_max * (float)K)), the division and the multiplication each rounded to fp32 in this order
+ * A non-finite or negative binned value goes to bin 0.  Counts are integer atomics from per-wave LDS histograms; the fp64 sums are
+ * per-workgroup partials in the workspace (fixed order inside a workgroup), folded by one workgroup in block order: no
+ * floating-point atomic, the same bits on every run.  One hipMemsetAsync and two launches; no allocation, no host synchronisation.
+ * workspace: 8-byte aligned, dycon_calibration_workspace(V, K) bytes (0 for arguments it rejects). */
+size_t dycon_calibration_workspace(long long V, int K);
+int dycon_calibration_counts(const float* prob, const uint8_t* label, const uint8_t* mask, const float* unc, float u_max, int C,
+                             long long V, int K, long long* counts, double* sums, void* workspace, size_t ws_bytes,
+                             dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- preprocessing: normalise and zoom (csrc/resample.hip;
  * code/BraTS19_DataPreprocessing.py:8-31, :175-198; code/ISLES22_DataPreprocessing.py:10-33, :141-159)
  * All volumes are C-contiguous fp32 (B, X, Y, Z) = B samples of V voxels, every sample with its own statistics.  NaN or infinite
