@@ -152,6 +152,15 @@ SIGNATURES = {
     "dycon_cc_largest": (I, [P, I, P, I, I, I, I, I, P, P, P, P, Z, P]),
     "dycon_lesion_workspace": (Z, [I, I, I, I]),
     "dycon_lesion_counts": (I, [P, P, I, I, I, I, I, P, P, Z, P]),
+    # csrc/morphology.hip: bit-packed binary morphology, hole filling and the component size filter (utils/morphology.py)
+    "dycon_morph_fill_workspace": (Z, [I, I, I, I]),
+    "dycon_cc_min_size_workspace": (Z, [I, I, I, I]),
+    "dycon_morph_pack": (I, [P, I, I, I, I, I, I, L, P, P]),
+    "dycon_morph_unpack": (I, [P, I, I, I, I, P, P]),
+    "dycon_morph_stencil": (I, [P, P, P, I, I, I, I, I, I, I, P]),
+    "dycon_morph_fill_holes": (I, [P, I, I, I, I, I, P, P, Z, P]),
+    "dycon_cc_keep_min_size": (I, [P, I, I, I, I, I, P, P, Z, P]),
+    "dycon_morph_merge_class": (I, [P, I, P, I, L, P, P]),
     "dycon_sdf_workspace": (Z, [I, I, I, I]),
     "dycon_sdf": (I, [P, I, I, I, I, I, I, I, I, I, I, P, P, Z, P]),
     "dycon_simhist_workspace": (Z, [I, I, I, I]),

@@ -17,43 +17,11 @@
 // keep their roots.  Integer atomics only, so every output is the same on every run.  No kernel waits on another workgroup; a call
 // is two hipMemsetAsync and three launches, allocates nothing and reads nothing back.
 #include "common.h"
+#include "root_counts.h"                          // les_wave_add, les_flush, les_root: shared with csrc/morphology.hip
 
 #define LES_MAX_AXIS 512                          // the limits of dycon_cc_roots
 #define LES_FIELDS 8
 enum { LES_N_GT, LES_N_PRED, LES_TP, LES_FN, LES_FP, LES_VOX_GT, LES_VOX_PRED, LES_VOX_AND };
-
-// arr[q - 1] += 1 for every lane with q != 0.  One large lesion is the common case and consecutive lanes walk z, so the lanes of a
-// wave mostly share a root: the wave loops on the root of its first pending lane, ballots the lanes that hold it and counts them
-// once (at most 64 rounds: the leader leaves the pending set every round; exactly 64 for 64 distinct roots).  The count is held in
-// (held, n), the same in every lane, and goes to memory by one atomicAdd of lane 0 only when the root changes or at les_flush:
-// a wave inside one lesion costs one atomic for its whole walk.  Integer adds: the sum does not depend on where an add went.
-__device__ __forceinline__ void les_wave_add(int* __restrict__ arr, int q, int lane, int& held, int& n) {
-    bool pending = q != 0;
-    for (;;) {
-        const unsigned long long todo = __ballot(pending);
-        if (!todo) break;                                    // wave-uniform
-        const int lq = __shfl(q, __ffsll(todo) - 1, 64);
-        const unsigned long long same = __ballot(pending && q == lq);
-        if (lq != held) {
-            if (n && lane == 0) atomicAdd(arr + held - 1, n);
-            held = lq;
-            n = 0;
-        }
-        n += __popcll(same);
-        if (q == lq) pending = false;
-    }
-}
-
-__device__ __forceinline__ void les_flush(int* __restrict__ arr, int lane, int held, int n) {
-    if (n && lane == 0) atomicAdd(arr + held - 1, n);
-}
-
-// a root of this volume, or 0: anything outside 1..V is background, so no value of a root map can address outside the workspace
-__device__ __forceinline__ int les_root(const int* __restrict__ r, long long i, long long V) {
-    if (i >= V) return 0;
-    const int q = r[i];
-    return (q >= 1 && q <= V) ? q : 0;
-}
 
 __global__ __launch_bounds__(256) void les_sizes_kernel(const int* __restrict__ root_p, const int* __restrict__ root_g, long long V,
                                                         int* __restrict__ size_p, int* __restrict__ size_g) {

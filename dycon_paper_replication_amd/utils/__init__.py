@@ -11,6 +11,7 @@ from . import eval_classes  # noqa: E402,F401
 from . import surface  # noqa: E402,F401
 from . import surface_eval  # noqa: E402,F401
 from . import components  # noqa: E402,F401
+from . import morphology  # noqa: E402,F401
 from . import device_eval  # noqa: E402,F401
 from . import lesions  # noqa: E402,F401
 from . import isles_eval  # noqa: E402,F401

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import components, metrics, surface
+from . import components, metrics, morphology, surface
 from .case_loop import dc_jc as _dc_jc, hd95_asd as _hd95_asd, mean_over_cases as _mean_over_cases
 from .sliding_window import _sliding_window, _stream, chunk_box  # noqa: F401  (chunk_box: public here, tools/eval_bench.py and the tests)
 
@@ -124,19 +124,23 @@ def calculate_metric_perclass(pred, gt, num_classes, device_surface=False, voxel
 
 def test_all_case_classes(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
                           preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, nms=0, voxelspacing=None,
-                          connectivity=1, *, blend=None):
+                          connectivity=1, *, postprocess=None, blend=None):
     """`test_all_case` (code/utils/test_3d_patch.py:251-291) with the all-class evaluator: cases as there; returns the mean (C-1, 4)
     (dice, jaccard, hd95, asd) per foreground class over the cases and writes `../performance.txt` the same way.  device_surface is
     passed to `calculate_metric_perclass`.  The reference defines `nms` for the class-1 map only (:19-26, :266-267); `nms` here is
     its per-class extension: each foreground class of the prediction keeps its largest component
     (`components.largest_component_per_class`, on the device) before the metrics.  The default, 0, leaves the prediction as it is.
     voxelspacing / connectivity go to `calculate_metric_perclass`; a case given as (image, label, spacing) carries its own spacing.
+    postprocess (`morphology.PostProcess`): the label map of every case goes through `postprocess.per_class` before `nms`.
     blend goes to `single_case_classes_device`."""
     surface.normalise_spacing(voxelspacing, connectivity)
+    morphology.check_postprocess(postprocess)
     def per_case(image, label, spacing):
         pred, score = single_case_classes_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, blend=blend)
         if score.shape[0] != num_classes:
             raise ValueError(f"num_classes = {num_classes}, the model has {score.shape[0]} classes")
+        if postprocess is not None:
+            pred = postprocess.per_class(pred, num_classes)
         if nms:
             pred = components.largest_component_per_class(pred, num_classes)
         return calculate_metric_perclass(pred, np.asarray(label), num_classes, device_surface=device_surface, voxelspacing=spacing,

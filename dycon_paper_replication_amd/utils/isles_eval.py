@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import lesions, sliding_window, surface_eval
+from . import lesions, morphology, sliding_window, surface_eval
 from . import test_3d_patch as _host
 
 CASE_FIELDS = ("dice", "hd95", "asd", "sensitivity", "specificity")
@@ -50,7 +50,7 @@ def isles_case_metrics(pred, gt, device_surface=True, voxelspacing=None):
 
 
 def evaluate_isles22(model, cases, patch_size=None, stride_xy=16, stride_z=4, batch_size=4, lesion=True, connectivity=3,
-                     min_voxels=1, label_key="mask", *, blend=None):
+                     min_voxels=1, label_key="mask", *, postprocess=None, blend=None):
     """The loop of code/test_ISLES22.py:78-180 over `cases` (h5 paths, (image, label) or (image, label, spacing), read by
     `surface_eval.read_case`; a case's spacing goes into its HD95, ASD and abs_volume_diff).
 
@@ -58,17 +58,21 @@ def evaluate_isles22(model, cases, patch_size=None, stride_xy=16, stride_z=4, ba
     a patch size runs the sliding window with the given strides.  Either way the prediction is the class-1 probability > 0.5
     (:88-91) as a device tensor.  With lesion=True every case also gets lesion_f1, lesion_count_diff and abs_volume_diff
     (utils/lesions.py; `connectivity`, `min_voxels`).  blend (`sliding_window.Blend`) blends overlapping windows, so it is valid on the
-    sliding-window route only: with patch_size=None a blend raises ValueError.
+    sliding-window route only: with patch_size=None a blend raises ValueError.  postprocess (`morphology.PostProcess`) is applied to
+    the prediction on the device before the voxel metrics and the lesion scores alike.
 
     Returns {"per_case": {name: float64 array over the cases}, "summary": {name: (np.mean, np.std)}} (:177-179)."""
     if patch_size is None and blend is not None:
         raise ValueError("blend needs the sliding window: the whole-volume forward (patch_size=None) has one window and nothing to blend")
+    morphology.check_postprocess(postprocess)
     names = CASE_FIELDS + (LESION_FIELDS if lesion else ())
     rows = {name: [] for name in names}
     for case in cases:
         image, label, spacing = surface_eval.read_case(case, label_key)
         window = tuple(image.shape) if patch_size is None else tuple(patch_size)
         pred, _ = sliding_window.single_case_device(model, image, stride_xy, stride_z, window, batch_size=batch_size, blend=blend)
+        if postprocess is not None:
+            pred = postprocess(pred)
         label = np.asarray(label)
         m = isles_case_metrics(pred, label, device_surface=True, voxelspacing=spacing)
         if lesion:

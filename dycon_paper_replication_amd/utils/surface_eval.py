@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import case_loop, components, sliding_window, surface
+from . import case_loop, components, morphology, sliding_window, surface
 from . import test_3d_patch as _host
 from .case_loop import read_case  # noqa: F401  (other modules read cases through this name)
 
@@ -51,27 +51,35 @@ def _own_loop(device_surface, voxelspacing, connectivity, cases):
 
 def test_all_case(model, cases, num_classes, patch_size=(96, 96, 64), stride_xy=16, stride_z=4, batch_size=4, metric_detail=0,
                   nms=0, preproc_fn=None, test_save_path=None, label_key="label", device_surface=False, voxelspacing=None,
-                  connectivity=1, *, blend=None):
+                  connectivity=1, *, postprocess=None, blend=None):
     """`test_3d_patch.test_all_case`; with device_surface=True, a spacing, a connectivity or a list holding (image, label, spacing)
     cases the same loop (:251-291) with `calculate_metric_percase` of this module per case.
 
     blend (`sliding_window.Blend`, not in the reference) runs the loop here as well.  With device_surface=True the blended loop is
     the device-resident one of `device_eval.test_all_case`: `single_case_device`, `components.largest_component` for `nms` and the
-    device metrics, with no host copy of the label map; otherwise the maps go through `test_single_case` to the host as before."""
+    device metrics, with no host copy of the label map; otherwise the maps go through `test_single_case` to the host as before.
+
+    postprocess (`morphology.PostProcess`, not in the reference) runs the loop here too: the label map of every case goes through it
+    on the device after the sliding window and before `nms`; on the route that holds the map on the host the result is copied back."""
     surface.normalise_spacing(voxelspacing, connectivity)
-    if blend is None and not _own_loop(device_surface, voxelspacing, connectivity, cases):
+    morphology.check_postprocess(postprocess)
+    if blend is None and postprocess is None and not _own_loop(device_surface, voxelspacing, connectivity, cases):
         return _host.test_all_case(model, cases, num_classes, patch_size, stride_xy, stride_z, batch_size=batch_size,
                                    metric_detail=metric_detail, nms=nms, preproc_fn=preproc_fn, test_save_path=test_save_path,
                                    label_key=label_key)
 
     def device_case(image, label, spacing):
         pred, _ = sliding_window.single_case_device(model, image, stride_xy, stride_z, patch_size, batch_size=batch_size, blend=blend)
+        if postprocess is not None:
+            pred = postprocess(pred)
         return case_loop.binary_case(pred, label, nms, components.largest_component, lambda p, g: calculate_metric_percase(
             p, g, device_surface=True, voxelspacing=spacing, connectivity=connectivity))
 
     def per_case(image, label, spacing):
         pred, _ = _host.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes, batch_size=batch_size,
                                          blend=blend)
+        if postprocess is not None:
+            pred = postprocess(pred).cpu().numpy().astype(pred.dtype)
         return case_loop.binary_case(pred, label, nms, _host.getLargestCC, lambda p, g: calculate_metric_percase(
             p, g, device_surface=device_surface, voxelspacing=spacing, connectivity=connectivity))
 

@@ -690,6 +690,47 @@ size_t dycon_lesion_workspace(int n_vol, int X, int Y, int Z);
 int dycon_lesion_counts(const int* root_pred, const int* root_gt, int n_vol, int X, int Y, int Z, int min_voxels, long long* counts,
                         void* workspace, size_t ws_bytes, dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- binary morphology on bit-packed masks (csrc/morphology.hip)
+ * scipy.ndimage's binary_erosion / binary_dilation (hence opening and closing), binary_fill_holes and a component size filter, bit
+ * for bit.  Shape limits are those of dycon_cc_roots: every axis 1..512, at most 65535 volumes and 2^31 - 1 voxels in one call.
+ *   packed : a mask (n_vol, X, Y, Z) as (n_vol, X, Y, W) uint64 words, W = ceil(Z / 64): bit b of word w of a row is the voxel
+ *            z = 64 w + b.  The bits z >= Z of a row's last word are 0 on entry and 0 after every operation.
+ *   pack   : vol uint8 or int64 (vol_bytes 1 or 8).  by_value == 0: a voxel is foreground when non-zero; otherwise when it equals
+ *            `value` (one class of a label map).  One wave ballot per word.
+ *   unpack : out uint8 (n_vol, X, Y, Z), 0 / 1.
+ *   stencil: `iterations` (1..64) erosions (op DYCON_MORPH_ERODE) or dilations (DYCON_MORPH_DILATE) by
+ *            generate_binary_structure(3, connectivity), connectivity 1, 2, 3 = 6, 18, 26 neighbours and the centre.  Voxels outside
+ *            the volume are background for both (scipy's border_value = 0).  The result is in `out`; `in` is left as it was;
+ *            `scratch` (the size of `out`; may be NULL for iterations == 1) is the other buffer of the ping-pong.  The three must not
+ *            overlap.  ceil(iterations / 4) launches: a workgroup stages 8 x 8 rows with a halo of up to 4 rows in LDS and runs up
+ *            to 4 iterations there, one thread per word; nothing is unpacked in between.
+ *   fill_holes: binary_fill_holes(mask, generate_binary_structure(3, connectivity)): the background is labelled with dycon_cc_roots at
+ *            that connectivity, a background component with a voxel on one of the six faces is marked, out = mask | every voxel of an
+ *            unmarked one.  workspace: dycon_morph_fill_workspace bytes.  Six launches and one hipMemsetAsync.
+ *   dycon_cc_keep_min_size: from a root map of dycon_cc_roots (a value outside 1..X*Y*Z is background): out uint8 = 1 on the
+ *            components of at least min_voxels (>= 1) voxels, 0 elsewhere.  workspace: dycon_cc_min_size_workspace bytes (one int32
+ *            per voxel, the sizes addressed by root - 1).  Two launches and one hipMemsetAsync.
+ *   merge_class: one step of the per-class recombination: where mask != 0, out = cls unless out already holds the voxel's own value
+ *            of label_map (uint8 or int64).  Called for cls = C-1 .. 1 on a zeroed out, a voxel ends with its original class when that
+ *            class's mask holds it, else with the smallest class whose mask does, else 0.
+ * Integers only (the marks are plain stores of one value, the sizes integer atomics): the same bits on every run.  No allocation, no
+ * host synchronisation, no workgroup waits on another. */
+#define DYCON_MORPH_ERODE 0
+#define DYCON_MORPH_DILATE 1
+size_t dycon_morph_fill_workspace(int n_vol, int X, int Y, int Z);
+size_t dycon_cc_min_size_workspace(int n_vol, int X, int Y, int Z);
+int dycon_morph_pack(const void* vol, int vol_bytes, int n_vol, int X, int Y, int Z, int by_value, long long value, uint64_t* packed,
+                     dycon_stream_t stream);
+int dycon_morph_unpack(const uint64_t* packed, int n_vol, int X, int Y, int Z, uint8_t* out, dycon_stream_t stream);
+int dycon_morph_stencil(const uint64_t* in, uint64_t* out, uint64_t* scratch, int n_vol, int X, int Y, int Z, int connectivity, int op,
+                        int iterations, dycon_stream_t stream);
+int dycon_morph_fill_holes(const uint64_t* mask, int n_vol, int X, int Y, int Z, int connectivity, uint64_t* out, void* workspace,
+                           size_t ws_bytes, dycon_stream_t stream);
+int dycon_cc_keep_min_size(const int* root, int n_vol, int X, int Y, int Z, int min_voxels, uint8_t* out, void* workspace,
+                           size_t ws_bytes, dycon_stream_t stream);
+int dycon_morph_merge_class(const void* label_map, int vol_bytes, const uint8_t* mask, int cls, long long n, uint8_t* out,
+                            dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- signed distance maps (csrc/sdf.hip)
  * compute_sdf of code/utils/util.py:205-236 for S = n_vol * n_cls maps in one set of launches.  labels: (n_vol, X, Y, Z) uint8 or
  * int64 (label_bytes 1 or 8), Z innermost, every axis in 1..512.  Map s = v * n_cls + k takes volume v; its foreground is voxel != 0
