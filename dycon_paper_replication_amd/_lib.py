@@ -190,6 +190,12 @@ SIGNATURES = {
     "dycon_zoom": (I, [P, I, I, I, I, I, I, I, I, I, P, I, F, P, I, P, Z, P]),
     "dycon_assemble_batch_rot": (I, [P, P, P, I, I, I, I, P, P, I, P, I, I, P]),
     "dycon_rotate_nearest": (I, [P, P, I, I, I, I, P, P, P]),
+    # csrc/filters.hip (utils/filters.py) and csrc/warp.hip (dataloaders/device_warp.py)
+    "dycon_gaussian_filter_workspace": (Z, [I, I, I, I, I, I]),
+    "dycon_gaussian_filter": (I, [P, P, I, I, I, I, P, I, P, I, P, I, I, F, P, Z, P]),
+    "dycon_assemble_batch_warp": (I, [P, P, P, I, P, I, I, I, P, P, I, P, I, I, P]),
+    "dycon_warp_volume": (I, [P, I, I, I, P, I, I, I, I, I, P, P, P, P]),
+    "dycon_intensity_augment": (I, [P, P, L, P, P, I, P]),
     "dycon_kernel_timing": (I, [I]),
     "dycon_kernel_timing_count": (L, []),
     "dycon_kernel_timing_fetch": (I, [L, L, P, P, P]),

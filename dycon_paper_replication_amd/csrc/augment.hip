@@ -13,6 +13,7 @@
 // The source coordinates must round as scipy's C does: one operation, one rounding.  hipcc contracts a * b + c into an FMA by default
 // for device code; the pragma below switches that off for the whole file (the Makefile passes -ffp-contract=off for it as well).
 #include "common.h"
+#include "gather_store.h"
 
 #include <math.h>
 
@@ -39,33 +40,6 @@ __device__ __forceinline__ bool rot_source(int rx, int ry, int X, int Y, const d
     sx = (int)floor(cx + 0.5), sy = (int)floor(cy + 0.5);
     return true;
 }
-
-// elements 0 .. n - 1 of a group of four to p: one 16-byte store (4 bytes for 1-byte elements, two of 16 for 8-byte ones) when vec
-template <typename T> __device__ __forceinline__ void store_group(T* __restrict__ p, const T (&v)[4], int n, int vec) {
-    if (vec) {
-        if constexpr (sizeof(T) == 1) {
-            *reinterpret_cast<uchar4*>(p) = make_uchar4(v[0], v[1], v[2], v[3]);
-        } else if constexpr (sizeof(T) == 4) {
-            uint4 q;
-            __builtin_memcpy(&q, v, 16);
-            *reinterpret_cast<uint4*>(p) = q;
-        } else {
-            ulonglong2 q[2];
-            __builtin_memcpy(q, v, 32);
-            reinterpret_cast<ulonglong2*>(p)[0] = q[0];
-            reinterpret_cast<ulonglong2*>(p)[1] = q[1];
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (t < n) p[t] = v[t];
-    }
-}
-
-template <int BYTES> struct Elem;
-template <> struct Elem<1> { typedef uint8_t type; };
-template <> struct Elem<4> { typedef float type; };
-template <> struct Elem<8> { typedef long long type; };
 
 // blockIdx.y = output sample; blockIdx.x strides over its P0 * P1 rows x G groups of 4 elements, as assemble_batch_kernel of
 // datapath.hip does.  LB: label bytes (1 | 8); OB: one-hot element bytes (0: none | 1 | 4 | 8)

@@ -355,10 +355,23 @@ class DeviceBatchLoader:
                         library's counter-based Philox stream, NOT ``np.random.randn``'s, so this one is equal in distribution
                         only: the image of batch number n of the loader's life is
                         ``ops.add_noise(image, None, s, 2 * s, noise_seed, n << 32)`` of the noise-free image.  A non-zero mu is
-                        not offered.  The noisy image is written into the ring buffer, so the two-batch lifetime holds."""
+                        not offered.  The noisy image is written into the ring buffer, so the two-batch lifetime holds.
+
+    Interpolating augmentations, not in the reference (dataloaders/device_warp.py); with both None nothing of the above changes,
+    calls, draws and bits:
+      warp=Warp(...)    random scale and rotation about all three axes with linear interpolation (labels: nearest) and elastic
+                        deformation, as scipy's affine_transform / map_coordinates compute them: `draw_plan_warp` /
+                        `assemble_batch_warp`.
+      intensity=Intensity(...)   Gaussian blur (scipy's gaussian_filter) of the drawn samples, then gain, bias and gamma.
+    Neither goes together with rot=True (ValueError): Warp has its own rotation.
+    Order within a batch: warp-assemble, blur, gain / bias / gamma, then noise_sigma.  The elastic field of batch number n is
+    ``elastic_field(B, patch, alpha, sigma, aug_seed, n << 32)`` for the drawn samples: Philox-based like the noise, so a run is
+    reproducible but the field equals no host stream.  All of it runs on the current stream into the ring buffers, with no host
+    synchronisation and no allocation after the first two batches."""
 
     def __init__(self, cache, batch_sampler, patch_size, rot_flip=True, label_dtype=torch.uint8, order="crop_rotflip",
-                 rot=False, onehot=None, onehot_dtype=torch.int64, noise_sigma=None, noise_seed=0):
+                 rot=False, onehot=None, onehot_dtype=torch.int64, noise_sigma=None, noise_seed=0, warp=None, intensity=None,
+                 aug_seed=0):
         if order not in ORDERS:
             raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
         if order == "rotflip_crop" and not rot_flip:
@@ -371,6 +384,15 @@ class DeviceBatchLoader:
         self.noise_sigma, self.noise_seed = noise_sigma, int(noise_seed)
         self.patch_size = tuple(int(v) for v in patch_size)
         self._ring, self._n, self._clean = [None, None], 0, None
+        self.warp, self.intensity, self._aug = warp, intensity, None
+        if warp is not None or intensity is not None:
+            from .device_warp import Intensity, LoaderAugment, Warp
+            if rot:
+                raise ValueError("rot=True is the reference's chain on its own: warp has its own rotation, and intensity goes with "
+                                 "the warp plan (Warp(p_affine=0) moves nothing)")
+            if not (warp is None or isinstance(warp, Warp)) or not (intensity is None or isinstance(intensity, Intensity)):
+                raise ValueError("warp must be None or a Warp, intensity None or an Intensity")
+            self._aug = LoaderAugment(aug_seed, cache.device)
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -380,13 +402,25 @@ class DeviceBatchLoader:
         shapes = self.cache.shapes
         if self.rot:
             from .device_augment import draw_plan_rot
+        if self._aug is not None:
+            from .device_warp import draw_plan_warp
         for batch in self.batch_sampler:
-            if self.rot:
+            if self._aug is not None:
+                yield draw_plan_warp(shapes, [int(i) for i in batch], self.patch_size, self.warp, self.intensity,
+                                     rot_flip=self.rot_flip, order=self.order)
+            elif self.rot:
                 yield draw_plan_rot(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
             else:
                 yield draw_plan(shapes, [int(i) for i in batch], self.patch_size, rot_flip=self.rot_flip, order=self.order)
 
     def _assemble(self, plan, out):
+        if self._aug is not None:
+            from .device_warp import assemble_batch_warp
+            out = assemble_batch_warp(self.cache, plan, out=out, displacement=self._aug.field(plan, self._n),
+                                      label_dtype=self.label_dtype, onehot=self.onehot, onehot_dtype=self.onehot_dtype)
+            if self.intensity is not None:
+                self._aug.values(plan, out["image"], *self.intensity.range)
+            return out
         if self.rot or self.onehot is not None:
             from .device_augment import assemble_batch_rot
             return assemble_batch_rot(self.cache, plan, out=out, label_dtype=self.label_dtype, onehot=self.onehot,

@@ -17,6 +17,7 @@ from . import lesions  # noqa: E402,F401
 from . import isles_eval  # noqa: E402,F401
 from . import util  # noqa: E402,F401
 from . import uncertainty  # noqa: E402,F401
+from . import filters  # noqa: E402,F401
 
 # the reference's two-model (`_plus`) evaluators, its LA validation loops and two small helpers (code/utils/test_3d_patch.py:14-17,
 # :28-49, :354-476, :488-494) live in utils/ensemble_eval.py, which imports test_3d_patch.py; they get the reference's module here

@@ -1011,6 +1011,69 @@ int dycon_assemble_batch_rot(const float* images, const uint8_t* labels, const d
 int dycon_rotate_nearest(const void* in, void* out, int elem_bytes, int X, int Y, int Z, const double* m, const double* off,
                          dycon_stream_t stream);
 
+/* ---------------------------------------------------------------- Gaussian filter (csrc/filters.hip; utils/filters.py)
+ * dycon_gaussian_filter is scipy.ndimage.gaussian_filter of N C-contiguous fp32 volumes (X, Y, Z), bit for bit.  The caller forms the
+ * weights as scipy does (fp64, r = int(truncate * sigma + 0.5), w = exp(-0.5 / sigma^2 * x^2) / sum for x = -r..r) and passes, per
+ * axis, a HOST pointer to the 2 r + 1 of them, read at call time, or NULL for an axis scipy skips (sigma 0).  The axes are filtered
+ * in the order 0, 1, 2, every intermediate is stored as fp32, and a line is summed in fp64 in scipy's symmetric form and order,
+ *     acc = x[c] * w[r];   for ii = -r .. -1:  acc += (x[c + ii] + x[c - ii]) * w[ii + r];   out = (float)acc
+ * with no fused multiply-add.  mode: how a line is extended (DYCON_FILTER_*; reflect wraps as often as r asks).  `scale` multiplies
+ * the fp32 result of the last pass in fp32 (1: the filter alone, same bits).  r <= DYCON_GAUSS_RMAX on every axis; weights that are
+ * not finite and exactly symmetric are rejected.  out == in filters in place; any other overlap is rejected.  The workspace holds
+ * dycon_gaussian_filter_workspace(N, X, Y, Z, filtered axes, out == in) bytes.  No atomics: bitwise reproducible. */
+#define DYCON_GAUSS_RMAX 64
+#define DYCON_FILTER_REFLECT 0
+#define DYCON_FILTER_CONSTANT 1
+#define DYCON_FILTER_NEAREST 2
+size_t dycon_gaussian_filter_workspace(int N, int X, int Y, int Z, int naxes, int inplace);
+int dycon_gaussian_filter(const float* in, float* out, int N, int X, int Y, int Z, const double* w0, int r0, const double* w1, int r1,
+                          const double* w2, int r2, int mode, float scale, void* workspace, size_t ws_bytes, dycon_stream_t stream);
+
+/* ---------------------------------------------------------------- interpolating warp and intensity (csrc/warp.hip;
+ * dataloaders/device_warp.py).  Not in the reference: the usual affine / elastic / intensity augmentations of 3-D segmentation,
+ * computed as scipy.ndimage.affine_transform / map_coordinates (mode='constant', cval=0) compute them.
+ * An output index (i0, i1, i2) has the source coordinate, in fp64, every operation rounded on its own (no fused multiply-add),
+ *     c_d = (((0.0 + i0 * m[3 d]) + i1 * m[3 d + 1]) + i2 * m[3 d + 2]) + off[d]      [+ (double)displacement_d(i0, i1, i2)]
+ * and the output is +0 unless 0 <= c_d <= n_d - 1 on all three axes.  Order 1: with f = floor(c), t = c - f, w0 = 1 - t and
+ * w1 = 1 - w0 the eight corners are summed from 0.0 in the order (0,0,0), (0,0,1), (0,1,0) .. (1,1,1), each as
+ * ((v[f + d] * wx) * wy) * wz, a corner at index n counting as 0, and the sum is rounded to the output type.  Order 0:
+ * v[floor(c + 0.5)].
+ *
+ * dycon_assemble_batch_warp: dycon_assemble_batch_rot with that source.  An output voxel is taken back through flip_axis and k to
+ * the patch index (a, b, z) as there; warp != 0: (i0, i1, i2) = (a, b, z), the image is read with the order-1 rule and the label with
+ * the order-0 rule (the caller puts the crop origin into off); warp == 0: the source is (ox + a, oy + b, oz + z) and the bits are
+ * dycon_assemble_batch's.  displacement (may be NULL): (njobs, 3, P0, P1, P2) fp32 on the device, read at (a, b, z) by the jobs
+ * with elastic != 0 (which need warp != 0).  Labels, one-hot planes, alignment and rejections are dycon_assemble_batch_rot's.
+ *
+ * dycon_warp_volume: one C-contiguous (X, Y, Z) device volume -> (O0, O1, O2).  order 1: elem_bytes 4 (fp32) or 8 (fp64); order 0:
+ * elem_bytes 1, 4 or 8, bytes are moved.  m (9, row-major) and off (3) are host pointers read at call time; displacement (may be
+ * NULL): (3, O0, O1, O2) fp32 on the device.  `out` must not overlap `in`.
+ *
+ * dycon_intensity_augment: for i in 0..n-1 the V fp32 voxels of sample samples[i] (NULL: sample i) of x, with the five doubles
+ * gain, bias, gamma, lo, hi = params[5 i ..] (host pointers, read at call time), in fp64, one rounding per operation:
+ *     v = (double)x * gain + bias;  v = clip(v, lo, hi);  u = (v - lo) / (hi - lo);  [gamma != 1: u = pow(u, gamma);]
+ *     y = (float)(u * (hi - lo) + lo)
+ * gamma > 0 and lo < hi are required.  y == x works in place; samples that are not named are not touched.
+ * All three are gathers or pointwise: no atomics, bitwise reproducible (pow is the device library's, not libm's). */
+typedef struct {
+    long long image_off, label_off; /* the fields of dycon_crop_job_t ... */
+    int X, Y, Z;
+    int ox, oy, oz;                 /* crop origin in stored coordinates (used when warp == 0) */
+    int k;
+    int flip_axis;
+    double m[9];                    /* ... and the transform: matrix, row-major */
+    double off[3];                  /* offset (holds the crop origin) */
+    int warp;                       /* 0: the plain crop (m, off ignored) */
+    int elastic;                    /* != 0: add the displacement (needs warp != 0) */
+} dycon_warp_job_t;
+int dycon_assemble_batch_warp(const float* images, const uint8_t* labels, const dycon_warp_job_t* jobs_host, int njobs,
+                              const float* displacement, int P0, int P1, int P2, float* out_image, void* out_label, int label_bytes,
+                              void* out_onehot, int onehot_classes, int onehot_bytes, dycon_stream_t stream);
+int dycon_warp_volume(const void* in, int X, int Y, int Z, void* out, int O0, int O1, int O2, int order, int elem_bytes,
+                      const double* m, const double* off, const float* displacement, dycon_stream_t stream);
+int dycon_intensity_augment(const float* x, float* y, long long V, const long long* samples, const double* params, int n,
+                            dycon_stream_t stream);
+
 /* ---------------------------------------------------------------- per-kernel timing (bench.py `roofline`; diagnostics)
  * dycon_kernel_timing(1): from now on every kernel this library launches is bracketed by two HIP timing events on its launch
  * stream (earlier records are dropped); (0): stop.  Each LAUNCH is one record -- the finalize / reduce launch an entry point
